@@ -13,16 +13,20 @@ Configs (--config sets the defaults, explicit flags override, the 
   C5            bs=8/GPU, SAM ViT-H + MSQP, T=14, 1024x1024 originals (fp8 GEMMs: --dtype fp8)
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full --dump-outputs out/
     python bench.py --gpus 8            # spawns the 8 ranks itself (torch.distributed.run on 127.0.0.1) before touching a GPU
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the headline (images/s, ms_per_step,
+the step's algorithmic GFLOP and its share of the bf16 peak).  --dump-outputs DIR writes what the last timed step computed (see
+dump_outputs).  --full adds, after the timed steps, the objects below:
   roofline      the dominant kernel (most GEMM time in a step): algorithmic FLOPs of all its launches in one step / the sum of
                 their durations, timed with HIP events on the launch stream in an instrumented, serialised (single-stream) step
                 that runs right after the timed region (same process, same buffers).  e2e_* = whole step.
   cpu_baseline  the CPU oracle (oracle/, fp32 PyTorch restatement pinned to the reference) timed on the host cores on a bounded
                 sample (one image of the batch: 1 warm-up + 3 timed runs), rank 0 at N=1 only.
-  secondary     (default C2 run at N=1 only) the other single-GPU configurations -- C3, C2 at T=14, C5 with fp8 -- as short passes in fresh
+  mask_decode   one image's decode chain alone on the GPU (mask_decode_ms): graph replay, staged and eager, median of 3 x 50 calls.
+  secondary     (C2 run at N=1 only) the other single-GPU configurations -- C3, C2 at T=14, C5 with fp8 -- as short passes in fresh
                 processes after the headline is final: [{config, images_per_s, ms_per_step, e2e_frac, steps}].  --no-secondary skips them.
 """
 import argparse
@@ -83,10 +87,16 @@ def parse(argv=None):
     ap.add_argument("--sam-split", type=int, default=1, help="the SAM encoder as this many independent slices of the batch, each on a stream of its own (WalkGPT.get_visual_emb_tokens(sub_batches=))")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--no-decode-graph", action="store_true", help="launch the decode chain eagerly instead of replaying its captured HIP graph")
-    ap.add_argument("--steps-only", action="store_true", help="profiling runs: warm-up + timed steps only (no latency / instrumented / CPU passes)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short secondary passes (C3, C2 at T=14, C5 fp8) the default N=1 run appends to its line")
+    ap.add_argument("--steps-only", action="store_true", help="profiling runs: warm-up + timed steps only, also with --full (no latency / instrumented / CPU passes)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure the one-image decode latency, the instrumented roofline step, "
+                                                        "the CPU baseline and (default C2 at N=1) the secondary configurations; off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the forward's outputs) to DIR/<name>.npy as float32, at most 64 MB in all")
+    ap.add_argument("--no-secondary", action="store_true", help="skip the short secondary passes (C3, C2 at T=14, C5 fp8) a --full N=1 run appends to its line")
     ap.add_argument("--probe-launch", action="store_true", help="self-test of the rank launch only: gloo rendezvous, no GPU work (tests/test_bench_launch.py)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     preset = CONFIGS[args.config]
     for k, v in preset.items():
         if getattr(args, k) is None:
@@ -218,6 +228,35 @@ def make_inputs(args, dev, rank):
     seg_hidden = [torch.randn(T, args.llm_hidden, generator=g).to(dev, torch.bfloat16) for _ in range(B)]
     return dict(images=images, images_clip=images_clip, seg_hidden=seg_hidden, resize_list=[(1024, 1024)] * B,
                 original_size_list=[(args.original, args.original)] * B, clip_resize_list=[(448, 448)] * B)
+
+
+DUMP_BYTES = 64 * 1000 * 1000   # all files of one --dump-outputs together
+
+
+def dump_outputs(path, arrays, seed=0):
+    """Write each tensor of `arrays` (name -> device tensor) to path/<name>.npy as float32, at most DUMP_BYTES in all.
+
+    Smaller arrays are written whole, in their shape.  When the rest does not fit, each larger one gets an equal share of what is left
+    and is written as a 1-D sample of `share` elements of the flattened array: one from each of `share` equal consecutive ranges, at an
+    offset drawn by a generator seeded from `seed` and the name, so the same shapes give the same indices in every run."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    budget = (DUMP_BYTES - 256 * len(arrays)) // 4                       # float32 elements (256 bytes: room for each .npy header)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(items):
+        share = budget // (len(items) - i)
+        t = t.detach()
+        if t.numel() > share:
+            lo = np.arange(share + 1, dtype=np.int64) * t.numel() // share              # range k is [lo[k], lo[k + 1]), never empty
+            rng = np.random.default_rng([seed, zlib.crc32(name.encode())])
+            idx = lo[:-1] + (rng.random(share) * (lo[1:] - lo[:-1])).astype(np.int64)
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.float().cpu().numpy()
+        budget -= a.size
+        np.save(os.path.join(path, name + ".npy"), a)
+        note("dumped %s %s (%s)" % (name, tuple(a.shape), "whole" if a.size == arrays[name].numel() else "sample of %d" % arrays[name].numel()))
 
 
 def usable_cpus():
@@ -449,6 +488,7 @@ def main():
             cur = torch.cuda.current_stream()
             use_side = side is not None and not serial
             tails = bool(args.tail_tiles)
+            pre = []    # the tower's second output (per CLIP sub-batch), kept for --dump-outputs
             if use_side and args.clip_split > 1:
                 # experiment: independent sub-batches of the tower on streams of their own (finer interleaving of the persistent kernels)
                 per = B // args.clip_split
@@ -456,9 +496,10 @@ def main():
                 for k, sk in enumerate(clip_streams):
                     sk.wait_stream(cur)
                     with torch.cuda.stream(sk):
-                        f, _pre = model.encode_images_clip(inp["images_clip"][k * per:(k + 1) * per], inp["clip_resize_list"][k * per:(k + 1) * per],
-                                                           tail_tiles=tails)
+                        f, p = model.encode_images_clip(inp["images_clip"][k * per:(k + 1) * per], inp["clip_resize_list"][k * per:(k + 1) * per],
+                                                        tail_tiles=tails)
                         parts.append(f)
+                        pre.append(p)
                 for sk in clip_streams[1:]:
                     side.wait_stream(sk)
                 with torch.cuda.stream(side):
@@ -466,12 +507,13 @@ def main():
             elif use_side:
                 side.wait_stream(cur)
                 with torch.cuda.stream(side):
-                    feats, _pre = model.encode_images_clip(inp["images_clip"], inp["clip_resize_list"], tail_tiles=tails)
+                    feats, p = model.encode_images_clip(inp["images_clip"], inp["clip_resize_list"], tail_tiles=tails)
+                    pre.append(p)
             else:
-                feats, _pre = model.encode_images_clip(inp["images_clip"], inp["clip_resize_list"], tail_tiles=tails)
+                feats, p = model.encode_images_clip(inp["images_clip"], inp["clip_resize_list"], tail_tiles=tails)
+                pre.append(p)
             emb = model.get_visual_emb_tokens(inp["images"], sub_batches=1 if serial or side is None else args.sam_split)
-            if args.with_msqp:
-                model.project_visual_tokens(emb)
+            vis = model.project_visual_tokens(emb) if args.with_msqp else None
 
             def decode_part():
                 if record_decode:
@@ -495,7 +537,7 @@ def main():
                 cur.wait_stream(side)         # keep at most one CLIP pass in flight per step
             else:
                 masks, scores = decode_part()
-        return feats, masks, scores, emb
+        return feats, masks, scores, emb, pre, vis
 
     def fence():
         torch.cuda.synchronize()
@@ -514,8 +556,9 @@ def main():
     fence()
     note("timed region: %d steps" % args.steps)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step(record_decode=True)
+    last = step(record_decode=True)    # what the last step computed stays referenced for --dump-outputs
     t_enq = time.perf_counter() - t0   # host time to enqueue the launches of all steps (no synchronisation inside)
     fence()
     elapsed = time.perf_counter() - t0
@@ -526,21 +569,43 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     images_per_s = world * B * args.steps / elapsed
     decode_batch_ms = sum(a.elapsed_time(b) for a, b in decode_ev) / max(1, len(decode_ev))
+    note("%.2f images/s, %.3f ms/step" % (images_per_s, ms_per_step))
 
+    out = {"metric": "images/sec", "value": round(images_per_s, 2), "unit": "images/s", "n_gpus": world,
+           "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+           "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+           "e2e_algorithmic_gflop_per_step": round(gflop_per_step(args), 1), "e2e_peak": PEAK_TF["bf16"],
+           "e2e_frac": round(gflop_per_step(args) / ms_per_step / PEAK_TF["bf16"], 4),      # per GPU: GFLOP / ms == TFLOP/s
+           "host_enqueue_ms_per_step": round(t_enq / args.steps * 1e3, 3),
+           "rccl_ranks": world if dist is not None else 0,
+           "config": {"workload": workload_label(args, world), "global_batch": world * B, "batch_per_gpu": B, "seg_tokens_per_image": T,
+                      "parallelism": "dp%d (images sharded, RCCL all-gather of mask logits)" % world if world > 1 else "single GPU"}}
     if args.steps_only:
+        out["steps_only"] = True
+
+    if args.dump_outputs and rank == 0:
+        # the forward's outputs (WalkGPTGrounding.forward: clip_features, clip_pre_features, visual_tokens, pred_masks, mask_scores)
+        feats, masks, scores, _emb, pre, vis = last
+        arrays = {"clip_features": feats, "clip_pre_features": torch.cat([p[0] for p in pre], 0),
+                  "pred_masks": torch.stack(list(masks), 0), "mask_scores": torch.stack(list(scores), 0)}
+        if vis is not None:
+            arrays["visual_tokens"] = vis
+        if gathered is not None:
+            arrays["gathered_mask_logits"] = gathered
+        dump_outputs(args.dump_outputs, arrays)
+        del arrays, feats, masks, scores, _emb, pre, vis
+    del last
+
+    if not args.full or args.steps_only:
         if rank == 0:
-            print(json.dumps({"metric": "images/sec", "value": round(images_per_s, 2), "unit": "images/s", "n_gpus": world, "steps": args.steps,
-                              "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "dtype": args.dtype, "steps_only": True,
-                              "e2e_algorithmic_gflop_per_step": round(gflop_per_step(args), 1), "e2e_peak": PEAK_TF["bf16"],
-                              "e2e_frac": round(gflop_per_step(args) / ms_per_step / PEAK_TF["bf16"], 4),      # per GPU: GFLOP / ms == TFLOP/s
-                              "config": {"workload": workload_label(args, world)}}), flush=True)
+            print(json.dumps(out), flush=True)
         if dist is not None:
             dist.destroy_process_group()
         return 0
 
     # ---- mask-decode latency of ONE image (its T prompts) on an otherwise idle GPU: what BASELINE's "mask-decode ms" names --------
-    note("%.2f images/s; single-image decode latency" % images_per_s)
-    _f, _m, _s, emb = step(serial=True)
+    note("single-image decode latency")
+    _f, _m, _s, emb, _p, _v = step(serial=True)
     torch.cuda.synchronize()
     one = (emb[:1].contiguous(), inp["seg_hidden"][:1], inp["resize_list"][:1], inp["original_size_list"][:1])
     lat = {}
@@ -625,22 +690,15 @@ def main():
         except (OSError, KeyError, ValueError):
             pass
 
-    out = {"metric": "images/sec", "value": round(images_per_s, 2), "unit": "images/s", "n_gpus": world,
-           "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-           "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-           "mask_decode_ms": round(lat["graph"], 3),
-           "mask_decode": {"one_image_latency_ms": round(lat["graph"], 3), "one_image_latency_staged_ms": round(lat["graph_staged"], 3),
-                           "one_image_latency_eager_ms": round(lat["eager"], 3),
-                           "amortised_ms_per_image": round(decode_batch_ms / B, 3), "batch_ms_overlapped": round(decode_batch_ms, 3),
-                           "prompts_per_image": T,
-                           "note": "latency (median of 3 runs of 50 calls after 20 untimed ones): prompt encoder + mask decoder + postprocess of one image's T prompts alone on the GPU (CTP included), graph "
-                                   "replay with the embedding and [SEG] states resident in the graph's input buffers (staged: + the two copies into them); "
-                                   "amortised: the batch's decode chain as timed inside the step, overlapped with the next step's encoders, / images"},
-           "host_enqueue_ms_per_step": round(t_enq / args.steps * 1e3, 3),
-           "rccl_ranks": world if dist is not None else 0,
-           "config": {"workload": workload_label(args, world), "global_batch": world * B, "batch_per_gpu": B, "seg_tokens_per_image": T,
-                      "parallelism": "dp%d (images sharded, RCCL all-gather of mask logits)" % world if world > 1 else "single GPU"},
-           "roofline": roofline}
+    out.update({"mask_decode_ms": round(lat["graph"], 3),
+                "mask_decode": {"one_image_latency_ms": round(lat["graph"], 3), "one_image_latency_staged_ms": round(lat["graph_staged"], 3),
+                                "one_image_latency_eager_ms": round(lat["eager"], 3),
+                                "amortised_ms_per_image": round(decode_batch_ms / B, 3), "batch_ms_overlapped": round(decode_batch_ms, 3),
+                                "prompts_per_image": T,
+                                "note": "latency (median of 3 runs of 50 calls after 20 untimed ones): prompt encoder + mask decoder + postprocess of one image's T prompts alone on the GPU (CTP included), graph "
+                                        "replay with the embedding and [SEG] states resident in the graph's input buffers (staged: + the two copies into them); "
+                                        "amortised: the batch's decode chain as timed inside the step, overlapped with the next step's encoders, / images"},
+                "roofline": roofline})
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         note("cpu baseline (oracle on %d host threads)" % (args.cpu_threads or usable_cpus()))
         out["cpu_baseline"] = cpu_baseline(args)

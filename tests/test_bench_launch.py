@@ -39,3 +39,37 @@ def test_workload_labels_follow_the_arguments():
     assert bench.config_name(bench.parse(["--sam", "vit_l"]), 1) == "custom"
     a = bench.parse(["--config", "C3"])
     assert (a.batch, a.sam, a.seg_tokens, a.with_msqp) == (32, "vit_h", 14, True)
+
+
+def test_plain_run_is_lean_and_extras_need_full():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+    r = _run(["--steps", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_dump_outputs_cap_shapes_and_fixed_sample(tmp_path, monkeypatch):
+    """Small arrays whole in their shape; the rest as a seeded sample that spans the array; all files within the cap; same indices every run."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 40000)
+    big = torch.arange(20000, dtype=torch.float32).reshape(4, 5000)
+    arrays = {"scores": torch.tensor([[0.5], [0.25]]), "masks": torch.ones(3, 8, 8, dtype=torch.bfloat16), "feats": big}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["feats.npy", "masks.npy", "scores.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 40000
+    assert np.array_equal(np.load(tmp_path / "a" / "scores.npy"), arrays["scores"].numpy())
+    m = np.load(tmp_path / "a" / "masks.npy")
+    assert m.dtype == np.float32 and m.shape == (3, 8, 8) and (m == 1).all()
+    s, s2 = np.load(tmp_path / "a" / "feats.npy"), np.load(tmp_path / "b" / "feats.npy")
+    assert s.dtype == np.float32 and s.ndim == 1 and 0 < s.size < big.numel()
+    assert np.array_equal(s, s2)                                              # fixed sample
+    assert (np.diff(s) > 0).all() and s[0] < big.numel() / s.size and s[-1] >= big.numel() * (1 - 1 / s.size)   # spans the array
