@@ -218,9 +218,9 @@ def test_mx_scale_plane_layout_host_side():
     assert d.shape == (M, K) and float(d[129, 40]) == 8.0 and float(d[129, 3]) == 1.0 and float(d[0, 40]) == 1.0
 
 
-@pytest.mark.parametrize("source", ["walkgpt_amd/csrc/attn_pipe.hip", "tools/micro/gemm_fr.hip"])
+@pytest.mark.parametrize("source", ["walkgpt_amd/csrc/attn_pipe.hip"])
 def test_hand_placed_streams_have_no_unpadded_mfma_operand(source):
-    """attn_pipe.hip (product) and the gemm_fr.hip probe place the instructions of their loops as `asm volatile` statements; hipcc's hazard recogniser cannot see
+    """attn_pipe.hip places the instructions of its loop as `asm volatile` statements; hipcc's hazard recogniser cannot see
     that a statement is an MFMA, so neither a vector instruction the COMPILER emits directly in front of one that reads its result, nor
     compiler code reading an asm MFMA's result behind it, gets wait states (found the hard way: stale operands, wrong rows that came and went
     with the register allocation).  The lint compiles the file with the product build's flags and scans the ISA for both patterns."""
@@ -229,6 +229,34 @@ def test_hand_placed_streams_have_no_unpadded_mfma_operand(source):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "lint_asm_hazards.py"), os.path.join(ROOT, *source.split("/"))],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
+
+
+def test_environment_and_macros_choose_no_code_path():
+    """What the library and the host path compute depends on their arguments alone: no environment variable picks a kernel, tile order or
+    fusion, and the only compile-time switches left are the diagnostic stamp builds.  The build may read HIPCC / WG_EXTRA_HIPCC_FLAGS and
+    the loader WG_LIB (which compiler, which library file), nothing else."""
+    pkg = os.path.join(ROOT, "walkgpt_amd")
+    csrc = os.path.join(pkg, "csrc")
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith((".hip", ".h")):
+            continue
+        txt = open(os.path.join(csrc, name)).read()
+        assert "getenv(" not in txt, "csrc/%s reads the environment" % name
+        for cond in re.findall(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b(.*)$", txt, flags=re.M):
+            macros = set(re.findall(r"\bWG_[A-Z0-9_]+", cond.split("//")[0]))
+            assert macros <= {"WG_GEMM_STAMP", "WG_ATTN_STAMP"}, "csrc/%s: #if on %s" % (name, sorted(macros))
+    allowed = {"_build.py": {"HIPCC", "WG_EXTRA_HIPCC_FLAGS"}, "_lib.py": {"WG_LIB"}}
+    for dirpath, _, files in os.walk(pkg):
+        for name in files:
+            if not name.endswith(".py"):
+                continue
+            txt = open(os.path.join(dirpath, name)).read()
+            rel = os.path.relpath(os.path.join(dirpath, name), pkg)
+            if rel in allowed:
+                assert set(re.findall(r"os\.environ\.get\(\"(\w+)\"", txt)) <= allowed[rel]
+                assert txt.count("os.environ") == len(re.findall(r"os\.environ\.get\(\"\w+\"", txt)), rel
+            else:
+                assert "os.environ" not in txt and "getenv(" not in txt, "walkgpt_amd/%s reads the environment" % rel
 
 
 def test_epilogue_gelu_fit_is_within_its_stated_error():

@@ -1,4 +1,4 @@
-"""Lint of the hand-placed instruction streams (attn_pipe.hip, gemm_fr.hip): hipcc's hazard recogniser treats an `asm volatile` statement as
+"""Lint of the hand-placed instruction streams (attn_pipe.hip): hipcc's hazard recogniser treats an `asm volatile` statement as
 opaque, so neither side of a hazard that crosses its boundary gets wait states.  Compiles the file with the product build's flags
 (-save-temps) and reports
   A. every asm MFMA whose A / B / C operand overlaps the destination of a compiler-emitted vector instruction fewer than 2 wait states

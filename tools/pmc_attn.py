@@ -1,7 +1,10 @@
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from walkgpt_amd import ops
+from walkgpt_amd import _lib, ops
+# argument: wg_attn_pipe_mode (0 = the one-chain kernels only, 1 = the pipelined kernel for SAM global attention: the default)
+if len(sys.argv) > 1:
+    _lib.lib().wg_attn_pipe_mode(int(sys.argv[1]))
 dev = torch.device("cuda:0")
 B, heads, hd, grid = 8, 12, 64, 64
 D = heads * hd

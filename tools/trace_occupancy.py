@@ -18,7 +18,7 @@ for r in rows:
     by_regs = max(1, (per_simd * 4) // waves)
     by_lds = (160 * 1024) // lds if lds > 0 else 99      # (static LDS only: dynamic allocations are not in the trace)
     name = r["Kernel_Name"]
-    if "wg_gemm_pp_persist_kernel" in name or "wg_attn_window_unit_kernel" in name or "wg_gemm_fr_kernel" in name:
+    if "wg_gemm_pp_persist_kernel" in name or "wg_attn_window_unit_kernel" in name:
         by_lds = 1                                         # 130-160 KiB of dynamic LDS
     elif "wg_gemm_persist_kernel<128, 128" in name or "wg_gemm_kernel<128, 128" in name:
         by_lds = 2

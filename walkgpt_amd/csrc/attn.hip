@@ -1111,11 +1111,6 @@ extern "C" int wg_mha_bf16(const void* Q, long ldq, long q_rows_per_batch, const
 // SAM ViT attention over a packed qkv buffer [B*Hg*Hg, 3*D] (q | k | v, heads contiguous inside each third).
 // window == Hg: global attention; window < Hg: non-overlapping windows with zero padding to a multiple of
 // `window`, pad positions acting as keys/values equal to qkv_bias (their outputs are dropped).
-// WG_ATTN_WIN_UNIT=0: head_dim-64 windows on the tile-ahead kernel (A/B runs)
-static bool wg_window_unit_on() {
-    static const char* e = getenv("WG_ATTN_WIN_UNIT");
-    return !(e && e[0] == '0');
-}
 
 static int wg_sam_attn_impl(const void* qkv, const void* qkv_bias, const void* rel_pos_h, const void* rel_pos_w, void* out, void* out_q, void* out_mx, long mx_pitch,
                             int B, int grid, int window, int heads, int head_dim, float scale, void* stream);
@@ -1136,7 +1131,7 @@ extern "C" int wg_sam_attn_mx_supported(int B, int grid, int window, int heads, 
     AttnArgs a{};
     a.B = B; a.heads = heads; a.Hg = grid; a.nW = (grid + window - 1) / window; a.ldo = (long)heads * head_dim;
     if (window == 64) return wg_attn_pipe_takes(a, head_dim, 64, 8) ? 1 : 0;
-    if (window == 14) return (wg_window_unit_on() && wg_attn_window_unit_takes(a)) ? 1 : 0;
+    if (window == 14) return wg_attn_window_unit_takes(a) ? 1 : 0;
     return 0;
 }
 extern "C" int wg_sam_attn_relpos_mx_bf16(const void* qkv, const void* qkv_bias, const void* rel_pos_h, const void* rel_pos_w, void* out_q, void* out_mx, long mx_pitch,
@@ -1167,14 +1162,8 @@ static int wg_sam_attn_impl(const void* qkv, const void* qkv_bias, const void* r
 #define WG_SAM_CASE(HD_, S_, NW_)                                  \
     if (head_dim == HD_ && window == S_) {                         \
         a.qchunks = (qblocks + NW_ - 1) / NW_;                     \
-        if (S_ == 64 && wg_attn_pipe_takes(a, head_dim, S_, NW_)) {                                              \
-            /* (WG_ATTN_PIPE_NW=4: two four-wave workgroups per CU instead of one of eight waves -- measured equal, 577 vs 573 us) */ \
-            static const char* nwe = getenv("WG_ATTN_PIPE_NW");                                                  \
-            const int pnw = (nwe && nwe[0] == '4') ? 4 : 8;                                                      \
-            a.qchunks = (qblocks + pnw - 1) / pnw;                                                               \
-            return wg_attn_pipe_launch(a, S_, pnw, st);                                                          \
-        }                                                                                                        \
-        if (HD_ == 64 && S_ == 14 && wg_window_unit_on() && wg_attn_window_unit_takes(a)) return wg_attn_window_unit_launch(a, groups, st);      \
+        if (S_ == 64 && wg_attn_pipe_takes(a, head_dim, S_, NW_)) return wg_attn_pipe_launch(a, S_, NW_, st);                      \
+        if (HD_ == 64 && S_ == 14 && wg_attn_window_unit_takes(a)) return wg_attn_window_unit_launch(a, groups, st);      \
         if constexpr (S_ <= 32) return launch_attn_window<HD_, S_, NW_>(a, groups, st);   \
         else return launch_attn<HD_, S_, NW_>(a, groups, st);      \
     }

@@ -38,11 +38,7 @@ template <int HD> __device__ __forceinline__ int swzV(int row) {
 
 // raw v_exp_f32: exp2f() adds a denormal-range fix-up (compare, select, ldexp) around it that triples the cost of the
 // one instruction softmax cannot avoid; arguments here are <= RESCALE_THR and results below 2^-126 may flush to zero.
-#if defined(WG_ATTN_ABL) && WG_ATTN_ABL == 1
-__device__ __forceinline__ float wg_exp2(float x) { return x * 0.001f; }   // ablation build: no exponentials
-#else
 __device__ __forceinline__ float wg_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-#endif
 
 // ds_read_b64_tr_b16 through inline asm.  The builtin form makes hipcc park an `s_waitcnt vmcnt(0)` in front of the
 // first transposed read (it cannot tell the V tile being read from the LDS-DMA still writing the NEXT tile), which

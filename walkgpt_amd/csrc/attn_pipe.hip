@@ -644,14 +644,10 @@ static int launch_pipe(const AttnArgs& a, hipStream_t st) {
 
 // Which cases the pipelined kernel takes: 0 none, 1 (default) SAM global attention only -- the case it wins (580 vs 604 us at B = 8, 12 heads) --,
 // 2 also plain attention without a key bias on whole 64-key tiles (+ at most the one lone key), an even number >= 4 of them: measured equal to
-// wg_attn_kernel there (CLIP 55.2 vs 54.5 us, 4096 keys 663 vs 640), kept for the tests and for other chips.  WG_ATTN_PIPE in the environment
-// sets the initial mode; wg_attn_pipe_mode() changes it (returns the previous one; a negative argument only queries).
-static int g_pipe_mode = -1;
+// wg_attn_kernel there (CLIP 55.2 vs 54.5 us, 4096 keys 663 vs 640), kept for the tests and for other chips.  wg_attn_pipe_mode()
+// changes the mode (returns the previous one; a negative argument only queries).
+static int g_pipe_mode = 1;
 extern "C" int wg_attn_pipe_mode(int mode) {
-    if (g_pipe_mode < 0) {
-        const char* e = getenv("WG_ATTN_PIPE");
-        g_pipe_mode = (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 1;
-    }
     const int prev = g_pipe_mode;
     if (mode >= 0 && mode <= 2) g_pipe_mode = mode;
     return prev;
@@ -659,12 +655,12 @@ extern "C" int wg_attn_pipe_mode(int mode) {
 bool wg_attn_pipe_takes(const AttnArgs& a, int head_dim, int S, int nw) {
     const int mode = wg_attn_pipe_mode(-1);
     if (mode == 0 || head_dim != 64 || (nw != 8 && nw != 4)) return false;
-    if (S == 64) return a.Hg == 64 && a.nW == 1;
+    if (S == 64) return nw == 8 && a.Hg == 64 && a.nW == 1;      // (SAM global attention: eight waves)
     if (mode < 2 || S != 0 || a.key_bias) return false;
     const int nt = a.Lk / 64;
     return (a.Lk % 64) <= 1 && nt >= 4 && (nt & 1) == 0;
 }
 int wg_attn_pipe_launch(const AttnArgs& a, int S, int nw, hipStream_t st) {
-    if (S == 64) return nw == 8 ? launch_pipe<64, 8>(a, st) : launch_pipe<64, 4>(a, st);
+    if (S == 64) return launch_pipe<64, 8>(a, st);
     return nw == 8 ? launch_pipe<0, 8>(a, st) : launch_pipe<0, 4>(a, st);
 }

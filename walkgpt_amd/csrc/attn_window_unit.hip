@@ -227,9 +227,7 @@ __global__ __launch_bounds__(NW * 64) void wg_attn_window_unit_kernel(AttnArgs a
                 }
             }
         };
-#if !(defined(WG_ATTN_WIN_ABL) && (WG_ATTN_WIN_ABL & 2))
         rel_pass(0);
-#endif
         asm volatile("" ::: "memory");
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
@@ -240,9 +238,7 @@ __global__ __launch_bounds__(NW * 64) void wg_attn_window_unit_kernel(AttnArgs a
             else relw_c[e] = wv;
         }
         asm volatile("" ::: "memory");
-#if !(defined(WG_ATTN_WIN_ABL) && (WG_ATTN_WIN_ABL & 2))
         rel_pass(1);
-#endif
         __builtin_amdgcn_wave_barrier();       // (the tables are wave-private)
 
         f32x16 ot[DB];
@@ -262,9 +258,6 @@ __global__ __launch_bounds__(NW * 64) void wg_attn_window_unit_kernel(AttnArgs a
             constexpr bool HALF = decltype(half_c)::value;
             constexpr int NE = HALF ? 16 : 32;
             const int buf = t;                 // (tile index inside the unit buffer)
-#if defined(WG_ATTN_WIN_ABL) && (WG_ATTN_WIN_ABL & 4)
-            if (t >= 0) return;
-#endif
 #pragma unroll
             for (int i = 0; i < RPT; ++i) rh[i] = relh_tab[t * RPT + i];
             const char* kbuf = kv + ub * UNIT + buf * TILE2;

@@ -142,21 +142,6 @@ __device__ __forceinline__ void wg_load_residual(u32x4* rres, __amdgpu_buffer_rs
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 
-// Experiment knobs of the persistent 256x256 kernel (diagnostic builds only, tools/build_variant.py): cache policy bits of its output
-// stores and of its operand loads (gfx950 aux: 1 = sc0, 2 = nt, 16 = sc1).  Default 0 = the plain policy.
-// WG_GEMM_TAIL (persistent bf16 kernel): MFMAs of a cluster issued BEHIND its hand-over barrier (0: the barrier closes the cluster)
-#ifndef WG_GEMM_TAIL
-#define WG_GEMM_TAIL 0
-#endif
-#ifndef WG_GEMM_C_AUX
-#define WG_GEMM_C_AUX 0
-#endif
-#ifndef WG_GEMM_A_AUX
-#define WG_GEMM_A_AUX 0
-#endif
-#ifndef WG_GEMM_W_AUX
-#define WG_GEMM_W_AUX 0
-#endif
 __device__ __forceinline__ void wg_mfma16_acc(f32x4& acc, bf16x8 a, bf16x8 b) { acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0); }
 
 // FP8 = true: the same kernel on e4m3 (OCP) operands.  A K slab is still 128 bytes per row -- 128 fp8 values instead of 64 bf16 -- so
@@ -1187,15 +1172,15 @@ __global__ __launch_bounds__(512, 2) void wg_gemm_pp_persist_kernel(GemmArgs g) 
             if (which < 2) {
                 const int i = which * 2 + u;
                 if constexpr (SEAM)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, WG_LDS_PTR(ldsW + (i * RPR + wave * RPI) * ROWB), 16, voffW, (int)(offW + i * rsW), 0, WG_GEMM_W_AUX);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, WG_LDS_PTR(ldsW + (i * RPR + wave * RPI) * ROWB), 16, voffW, (int)(offW + i * rsW), 0, 0);
                 else
-                    __builtin_amdgcn_global_load_lds(WG_GLOBAL_PTR(srcW[i] + offW), WG_LDS_PTR(ldsW + (i * RPR + wave * RPI) * ROWB), 16, 0, WG_GEMM_W_AUX);
+                    __builtin_amdgcn_global_load_lds(WG_GLOBAL_PTR(srcW[i] + offW), WG_LDS_PTR(ldsW + (i * RPR + wave * RPI) * ROWB), 16, 0, 0);
             } else {
                 const int i = (which - 2) + 2 * u;
                 if constexpr (SEAM)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(ars, WG_LDS_PTR(ldsA + (i * RPR + wave * RPI) * ROWB), 16, voffA, (int)(offA + i * rsA), 0, WG_GEMM_A_AUX);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(ars, WG_LDS_PTR(ldsA + (i * RPR + wave * RPI) * ROWB), 16, voffA, (int)(offA + i * rsA), 0, 0);
                 else
-                    __builtin_amdgcn_global_load_lds(WG_GLOBAL_PTR(srcA[i] + offA), WG_LDS_PTR(ldsA + (i * RPR + wave * RPI) * ROWB), 16, 0, WG_GEMM_A_AUX);
+                    __builtin_amdgcn_global_load_lds(WG_GLOBAL_PTR(srcA[i] + offA), WG_LDS_PTR(ldsA + (i * RPR + wave * RPI) * ROWB), 16, 0, 0);
             }
         }
     };
@@ -1489,28 +1474,14 @@ __global__ __launch_bounds__(512, 2) void wg_gemm_pp_persist_kernel(GemmArgs g) 
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            if (WG_GEMM_TAIL > 0 && ks * 16 + i * 4 + j == 32 - WG_GEMM_TAIL) {
-                                // The hand-over barrier WG_GEMM_TAIL MFMAs before the end of the cluster: the partner group (parked at this barrier
-                                // since its load half-phase ended) is released while this wave still has matrix work to issue, so the barrier's
-                                // release latency passes under the tail instead of under an idle matrix pipe.  The tail outranks the partner's
-                                // fresh cluster (priority 2 against 1: ties go to the older wave, which would starve a younger wave's tail).
-                                __builtin_amdgcn_sched_barrier(0);
-                                __builtin_amdgcn_s_setprio(2);
-                                __builtin_amdgcn_s_barrier();
-                                __builtin_amdgcn_sched_barrier(0);
-                            }
-                            wg_mfma16_acc(acc[4 * sc + i][j], wf2[j >> 1][j & 1][ks], af[i][ks]);
-                        }
+                        for (int j = 0; j < 4; ++j) wg_mfma16_acc(acc[4 * sc + i][j], wf2[j >> 1][j & 1][ks], af[i][ks]);
                 }
                 __builtin_amdgcn_s_setprio(0);
                 __builtin_amdgcn_sched_barrier(0);
                 // (the tile's last barrier -- group 1 behind its last cluster, group 0 one cluster earlier -- is left out in the seam flow: every LDS
                 // read of the tile was over at the barrier in front of that cluster, so group 0 starts its epilogue beside group 1's last
                 // MFMAs instead of idling through them)
-                if (FP8 || WG_GEMM_TAIL == 0) {
-                    if (!(SEAM && last && sc == 1 && grp == 1)) __builtin_amdgcn_s_barrier();
-                }
+                if (!(SEAM && last && sc == 1 && grp == 1)) __builtin_amdgcn_s_barrier();
             }
         };
         {
@@ -1667,7 +1638,7 @@ __global__ __launch_bounds__(512, 2) void wg_gemm_pp_persist_kernel(GemmArgs g) 
                 const int n = nbase + (el % CH) * 8;
                 const int off0 = n < g.N ? ((cm0 + wm * WTM + half * 64 + el / CH) * (int)g.ldc + n) * 2 : (int)0x80000000;
 #pragma unroll
-                for (int it = 0; it < NIT; ++it) __builtin_amdgcn_raw_buffer_store_b128(t[it], crs, off0 + it * RPSl * (int)g.ldc * 2, 0, WG_GEMM_C_AUX);
+                for (int it = 0; it < NIT; ++it) __builtin_amdgcn_raw_buffer_store_b128(t[it], crs, off0 + it * RPSl * (int)g.ldc * 2, 0, 0);
                 if constexpr (FP8) {
                     // one E8M0 scale per (row, 32 columns): the power of two at or above max|block| / 448 (no value saturates), byte
                     // 127 + its exponent; the four lanes of a quad hold one block of a row.  Scale bytes: rows r, r+16, .. of a 128-row
@@ -1761,7 +1732,7 @@ static int launch_pp_persist(GemmArgs& g, hipStream_t st) {
         if (g.col_block && (long)g.M * g.K * 2 > (128L << 20)) {
             // A (ViT-H at bs = 32: 335 MB) does not stay in the 256 MB Infinity Cache from one column block to the next, and its panels are 640 KiB:
             // narrow blocks then make every XCD stream 16 row panels at a time, at different rows than its neighbours.  What measured best on those
-            // shapes (tools/bench_gemm_colblock.py, notes/r06_experiments.md section 16): blocks of 4-10 tile columns that are a whole number of XCD
+            // shapes (notes/r06_experiments.md section 16): blocks of 4-10 tile columns that are a whole number of XCD
             // ranges (an XCD owns nwg / 8 consecutive tiles of the order: the XCDs then walk the SAME row panels at the same time, in different
             // column blocks, and share them through the Infinity Cache) -- lin1 (20 tile columns): 5, -6.6 % -- and plain row-major when no such
             // width exists (qkv, proj: -2 ... -3 % against blocks of 2).
@@ -1769,15 +1740,6 @@ static int launch_pp_persist(GemmArgs& g, hipStream_t st) {
             g.col_block = 0;
             for (int c = 4; c <= 10 && c < g.tiles_n; ++c)
                 if (((long)g.tiles_m * c * 8) % nwg == 0) { g.col_block = c; break; }
-        }
-        static const char* force = getenv("WG_GEMM_COLBLOCK");      // experiments: tile order override (0 = row-major)
-        if (force && *force) {
-            g.col_block = atoi(force);
-#ifndef WG_GEMM_EXPERIMENT
-            if (g.col_block < 0) g.col_block = 0;      // the timing-only orders (resident 4 x 4 tiles, row bands) exist in diagnostic builds only
-#else
-            if (g.col_block < -1 && (((-g.col_block) >> 4) == 0 || ((-g.col_block) & 15) == 0)) g.col_block = 0;      // band height / block width 0
-#endif
         }
     }
     constexpr int stage = 512 * 128, slab = 64 * (64 * 2 + 16);
@@ -1801,9 +1763,7 @@ static int launch_pp_persist(GemmArgs& g, hipStream_t st) {
     // Which flow (template parameter SEAM): the seamless one whenever the number of slabs is even (its first-slab request lands in buffer 0
     // during the last slab); the round-1..5 flow for odd nk.
     const int nk = g.K / 64;
-    bool seam = (nk & 1) == 0;
-    static const char* force_seam = getenv("WG_GEMM_SEAM");      // =0: the round-1..5 flow everywhere (A/B runs)
-    if (force_seam && *force_seam) seam = seam && atoi(force_seam) != 0;
+    const bool seam = (nk & 1) == 0;
 #define WG_PP_LAUNCH(LN_, ST_, F8_, BYTES_)                                                                                           \
     do {                                                                                                                              \
         if (seam) hipLaunchKernelGGL((wg_gemm_pp_persist_kernel<LN_, ST_, F8_, true>), dim3(grid), dim3(512), BYTES_, st, g);         \
@@ -2017,12 +1977,6 @@ static int wg_gemm_dispatch(const void* A, long lda, const void* W, long ldw, co
                            (!residual || (ldr % 8 == 0 && ((uintptr_t)residual & 15) == 0 && g.r_bytes != 0));
     const bool small_ops = (long)M * lda < (1L << 31) && (long)N * ldw < (1L << 31);
     if (tile == 11 && !(can_stage && small_ops)) tile = 1;
-    if (tile == 17) {   // the experimental one-barrier persistent kernel (tools/micro/gemm_fr.hip): diagnostic builds only (tools/build_variant.py <tag> -DWG_GEMM_FR)
-#ifdef WG_GEMM_FR
-        if (can_stage && small_ops && wg_gemm_fr_supports(g)) return wg_launch_gemm_fr(g, st);
-#endif
-        tile = 16;
-    }
     if (tile == 16 && !(can_stage && small_ops && wg_pp_operands_ok(M, N, lda, ldw) && (!bias || ((uintptr_t)bias % 16 == 0 && N % 8 == 0)))) {
         WG_REQUIRE(!(g.ln_part || g.stats_part || g.ln_stats), "gemm: this operand layout cannot take the persistent kernel's staged epilogue");
         tile = 14;

@@ -41,10 +41,8 @@ def _rows(t):
 
 
 import contextlib as _contextlib
-import os as _os
 import threading as _threading
 
-_FORCE_TILE = int(_os.environ.get("WG_GEMM_TILE", "0"))  # experiments only: force one GEMM tile variant
 _tls = _threading.local()  # per-thread measurement state (no module-level mutable switches: two models / threads never interact)
 
 
@@ -77,12 +75,7 @@ def gemm_tile_for(M, N, K, lda, ldw, ldc, ldr, tail_tiles=False):
     ok = K % 64 == 0 and N % 4 == 0 and N >= 16 and lda % 8 == 0 and ldw % 8 == 0 and ldc % 4 == 0 and ldr % 4 == 0
     if not ok:
         return 3
-    if _FORCE_TILE:
-        return _FORCE_TILE
     return _lib.lib().wg_gemm_pick_tile_mnk(M, N, K, 1 if tail_tiles else 0)
-
-
-ROW_PARTIALS = _os.environ.get("WG_ROW_PARTIALS", "1") != "0"   # experiments: 0 = always take the row statistics in their own pass
 
 
 def _forget_sidecars(t):
@@ -117,7 +110,7 @@ def linear(x, weight, bias=None, act=ACT_NONE, residual=None, res_row_mod=0, out
         assert Nr == N
     if bias is not None:
         assert bias.dtype == _BF16 and bias.numel() == N
-    if (row_partials and ROW_PARTIALS and not out_f32 and tile == 0 and not _FORCE_TILE and not tail_tiles
+    if (row_partials and not out_f32 and tile == 0 and not tail_tiles
             and _lib.lib().wg_gemm_row_partials_supported(M, N, K, lda, weight.stride(0), ldc)
             and (bias is None or bias.data_ptr() % 16 == 0) and (residual is None or (ldr % 8 == 0 and residual.data_ptr() % 16 == 0))):
         mpad = (M + 255) // 256 * 256
@@ -160,9 +153,6 @@ def layernorm(x, gamma, beta, eps, act=ACT_NONE, out=None):
     return out
 
 
-LN_FUSE = _os.environ.get("WG_LN_FUSE", "1") != "0"  # experiments: 0 = always run LayerNorm and GEMM as two kernels
-
-
 def fold_layernorm(gamma, beta, weight, bias):
     """Operands of ln_linear: the LayerNorm's affine map folded into the linear layer that consumes it.
     y = LN(x) W^T + b = rstd (x Wg^T - mean s) + b'  with  Wg = bf16(W gamma), s = row sums of Wg (fp32, of the ROUNDED
@@ -193,11 +183,11 @@ def ln_linear(x, fold, eps, act=ACT_NONE, tail_tiles=False):
     M, K, lda = _rows(x)
     N = fold["wg"].shape[0]
     L = _lib.lib()
-    if not (LN_FUSE and not _FORCE_TILE and L.wg_gemm_ln_supported(M, N, K, lda, K, N)):
+    if not L.wg_gemm_ln_supported(M, N, K, lda, K, N):
         return linear(layernorm(x, fold["gamma"], fold["beta"], eps), fold["weight"], fold["bias"], act=act, tail_tiles=tail_tiles)
     out = torch.empty(x.shape[:-1] + (N,), device=x.device, dtype=_BF16)
     rp = getattr(x, "_wg_row_partials", None)
-    if rp is not None and rp[2] == x._version and rp[3] == M and rp[4] == K and ROW_PARTIALS:
+    if rp is not None and rp[2] == x._version and rp[3] == M and rp[4] == K:
         # the GEMM that wrote x left its rows' partial sums (linear(..., row_partials=True)): no statistics pass
         part, mpad = rp[0], rp[1]
         ev = _timed(17, M, N, K)
@@ -230,7 +220,7 @@ def layernorm_linear(x, gamma, beta, eps, weight, bias=None, act=ACT_NONE, out_f
     M, K, lda = _rows(x)
     N = weight.shape[0]
     L = _lib.lib()
-    if _FORCE_TILE or not L.wg_gemm_skinny_ln_supported(M, N, K, lda, weight.stride(0), N):
+    if not L.wg_gemm_skinny_ln_supported(M, N, K, lda, weight.stride(0), N):
         return linear(x if gamma is None else layernorm(x, gamma, beta, eps), weight, bias, act=act, out_f32=out_f32)
     assert weight.shape[1] == K and weight.stride(1) == 1
     assert gamma is None or (gamma.dtype == _BF16 and beta.dtype == _BF16 and gamma.numel() == K and beta.numel() == K)

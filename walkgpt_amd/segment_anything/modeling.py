@@ -14,8 +14,6 @@ import math
 from functools import partial
 from typing import Optional, Tuple
 
-import os
-
 import torch
 import torch.nn as nn
 
@@ -204,7 +202,7 @@ class Block(nn.Module, _Prepared):
     def _build(self):
         a, m = self.attn, self.mlp
         w2 = m.lin2.weight
-        if (w2.shape[1] * 2) % 10240 == 0 and w2.is_cuda and os.environ.get("WG_LIN2_PAD", "1") != "0":      # (=0: A/B runs)
+        if (w2.shape[1] * 2) % 10240 == 0 and w2.is_cuda:
             # ViT-H's lin2 (K = 5120): weight rows on a 10 240-byte pitch camp on a few memory channels -- the same rows 128 bytes further apart run the
             # GEMM 10 % faster (tools/bench_gemm_pitch.py, notes/r06_experiments.md section 7; K = 3072 / 4096 rows measured no difference)
             buf = torch.empty(w2.shape[0], w2.shape[1] + 64, device=w2.device, dtype=w2.dtype)
