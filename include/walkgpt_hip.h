@@ -32,8 +32,10 @@ extern "C" {
 #define WG_ACT_QUICK_GELU 2 /* x*sigmoid(1.702x)    HF CLIP MLP (custom_clip.py:50, third-party transformers) */
 #define WG_ACT_RELU 3       /* nn.ReLU()            model/segment_anything/modeling/transformer.py:23, mask_decoder.py:186 */
 
-int wg_version(void);               /* major*10000 + minor*100 + patch; 201 = 0.2.1: same entry points and argument lists as 0.2.0 (which changed them
-                                     * against 0.1.0: INTEGRATION.md section 3); 0.2.1 = round 6's kernels (GELU form of the bf16 epilogues, above) */
+int wg_version(void);               /* major*10000 + minor*100 + patch; 300 = 0.3.0: adds wg_prompt_sparse_f32, wg_mask_embed_bf16 and
+                                     * wg_normalize_pad_bf16 (SAM's point / box / mask prompts, Sam.preprocess); no existing argument list changed.
+                                     * 201 = 0.2.1: same entry points and argument lists as 0.2.0 (which changed them against 0.1.0: INTEGRATION.md
+                                     * section 3); 0.2.1 = round 6's kernels (GELU form of the bf16 epilogues, above) */
 const char* wg_last_error(void);    /* thread-local, valid until the next failing call on this thread */
 
 /* C[M,N] = act(A[M,K] . W[N,K]^T + bias[N]) (+ R[m % res_row_mod or m, :]).  bf16 in, bf16 or fp32 out.
@@ -150,6 +152,28 @@ int wg_nchw_to_tokens_bf16(const void* x, void* y, int B, int HW, int C, void* s
 /* PositionEmbeddingRandom.forward (prompt_encoder.py:216-229) as rows [h*w, 2*num_feats] fp32 from the fp32 [2, num_feats] matrix. */
 int wg_dense_pe_f32(const float* gaussian, float* pe_tokens, int h, int w, int num_feats, void* stream);
 int wg_cast_f32_to_bf16(const float* x, void* y, long n, void* stream);
+
+/* ---- point / box / mask prompts and Sam.preprocess (0.3.0; csrc/prompt.hip) ----
+ * wg_prompt_sparse_f32: the sparse prompt rows of PromptEncoder.forward in one launch -- _embed_points (prompt_encoder.py:80-100), _embed_boxes
+ * (:102-112), the concatenation of forward (:150-186), PositionEmbeddingRandom.forward_with_coords / _pe_encoding (:196-214, :231-240).
+ * out fp32 [B, R, C], R = (N + pad) + 2 * (boxes != null) + T, rows in the reference's order: points, box corners, text.
+ *   coords [B,N,2] fp32 (x, y) in input-image pixels + labels [B,N] int32, or both null; pad: append the padding point (the reference pads when
+ *   boxes is None); boxes [B,4] fp32 (x1, y1, x2, y2) or null; text [B,T,C] bf16 (text_bf16) or fp32, or null (copied after the geometry rows);
+ *   gaussian [2, C/2] fp32; embed_table [5, C] fp32 = point_embeddings[0..3], not_a_point_embed; (img_h, img_w) = input_image_size.
+ *   Label -1: no positional term, + not_a_point; 0 / 1: + point_embeddings[0 / 1]; other labels: the bare positional term; box corner k:
+ *   + point_embeddings[2 + k].  At least one of coords / boxes. */
+int wg_prompt_sparse_f32(const float* coords, const int* labels, int B, int N, int pad, const float* boxes, const void* text, int T, int text_bf16,
+                         const float* gaussian, const float* embed_table, int C, int img_h, int img_w, float* out, void* stream);
+/* wg_mask_embed_bf16: PromptEncoder.mask_downscaling on `masks` (prompt_encoder.py:57-65, _embed_masks :114-117; LayerNorm2d common.py:31-43):
+ * Conv2d(1->4, k2 s2) -> LayerNorm2d(eps1) -> GELU(erf) -> Conv2d(4->16, k2 s2) -> LayerNorm2d(eps2) -> GELU -> Conv2d(16->256, k1), fused per
+ * output pixel (stages before the last in fp32).  masks fp32 [B,1,4h,4w] (16-byte aligned) -> out bf16 channel-last rows [B, h*w, 256] (the bytes of
+ * a channels_last [B,256,h,w] tensor).  params fp32, 4684 floats: conv1 w [4,1,2,2], b [4]; ln1 w, b [4]; conv2 w [16,4,2,2], b [16]; ln2 w, b
+ * [16]; conv3 w [256,16,1,1], b [256], each flattened in that order.  mask_in_chans != 16 or embed_dim != 256: WG_ERR_UNSUPPORTED. */
+int wg_mask_embed_bf16(const float* masks, const float* params, float eps1, float eps2, void* out, int B, int h, int w, int mask_in_chans,
+                       int embed_dim, void* stream);
+/* wg_normalize_pad_bf16: Sam.preprocess (sam.py:174-186): x [B,3,H,W] uint8 (x_u8) or fp32 -> out [B,3,S,S] bf16 = (x - mean_c) / std_c,
+ * zero padded right / bottom; mean, std: device fp32 [3]. */
+int wg_normalize_pad_bf16(const void* x, int x_u8, const float* mean, const float* std, void* out, int B, int H, int W, int S, void* stream);
 
 /* masks[t,k,Y,X] = sum_c hyper[t,first_mask+k,c] * up[t,c,Y,X] (mask_decoder.py:150-160); `up` is the pixel-shuffled
  * GEMM output of the two transposed convs: rows (t, y, x, dy, dx), columns (dy2, dx2, c), channels == 32. */

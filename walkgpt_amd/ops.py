@@ -382,6 +382,64 @@ def cast_bf16(x):
     return y
 
 
+def prompt_sparse(coords, labels, pad, boxes, text, gaussian, embed_table, image_size):
+    """Sparse prompt rows (wg_prompt_sparse_f32): coords [B,N,2] fp32 + labels [B,N] int32 (or None), boxes [B,4] fp32 (or None), text [B,T,C]
+    bf16 / fp32 (or None); gaussian [2, C/2] fp32, embed_table [5, C] fp32 -> fp32 [B, N + pad + 2 * has_box + T, C]."""
+    _need_gpu(coords, labels, boxes, text, gaussian, embed_table)
+    C = embed_table.shape[1]
+    assert gaussian.dtype == torch.float32 and gaussian.is_contiguous() and tuple(gaussian.shape) == (2, C // 2)
+    assert embed_table.dtype == torch.float32 and embed_table.is_contiguous() and embed_table.shape[0] == 5
+    B, N = (coords.shape[0], coords.shape[1]) if coords is not None else (boxes.shape[0], 0)
+    if coords is not None:
+        assert coords.dtype == torch.float32 and coords.is_contiguous() and coords.shape == (B, N, 2)
+        assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.shape == (B, N)
+    if boxes is not None:
+        assert boxes.dtype == torch.float32 and boxes.is_contiguous() and boxes.shape == (B, 4)
+    T = 0
+    if text is not None:
+        assert text.dtype in (_BF16, torch.float32) and text.is_contiguous() and text.dim() == 3 and text.shape[0] == B and text.shape[2] == C
+        T = text.shape[1]
+    R = (N + int(pad) if coords is not None else 0) + (2 if boxes is not None else 0) + T
+    out = torch.empty(B, R, C, device=embed_table.device, dtype=torch.float32)
+    rc = _lib.lib().wg_prompt_sparse_f32(_ptr(coords), _ptr(labels), B, N, int(pad), _ptr(boxes), _ptr(text), T, 1 if text is not None and
+                                         text.dtype == _BF16 else 0, gaussian.data_ptr(), embed_table.data_ptr(), C, int(image_size[0]),
+                                         int(image_size[1]), out.data_ptr(), _stream())
+    _lib.check(rc, "wg_prompt_sparse_f32")
+    return out
+
+
+def mask_embed(masks, params, eps1, eps2, mask_in_chans=16, embed_dim=256):
+    """PromptEncoder.mask_downscaling (wg_mask_embed_bf16): masks fp32 [B,1,4h,4w] -> bf16 channel-last rows [B, h*w, embed_dim];
+    params: the fp32 blob the C-ABI documents."""
+    _need_gpu(masks, params)
+    assert masks.dtype == torch.float32 and masks.is_contiguous() and masks.dim() == 4 and masks.shape[1] == 1
+    assert params.dtype == torch.float32 and params.is_contiguous()
+    B, _, H, W = masks.shape
+    if H % 4 or W % 4:
+        raise ValueError("mask inputs must be 4h x 4w (got %d x %d)" % (H, W))
+    h, w = H // 4, W // 4
+    out = torch.empty(B, h * w, embed_dim, device=masks.device, dtype=_BF16)
+    rc = _lib.lib().wg_mask_embed_bf16(masks.data_ptr(), params.data_ptr(), float(eps1), float(eps2), out.data_ptr(), B, h, w, mask_in_chans,
+                                       embed_dim, _stream())
+    _lib.check(rc, "wg_mask_embed_bf16")
+    return out
+
+
+def normalize_pad(x, mean, std, size, out=None):
+    """Sam.preprocess (wg_normalize_pad_bf16): x [B,3,H,W] uint8 or fp32, mean / std fp32 [3] -> bf16 [B,3,size,size]."""
+    _need_gpu(x, mean, std, out)
+    assert x.dtype in (torch.uint8, torch.float32) and x.is_contiguous() and x.dim() == 4 and x.shape[1] == 3
+    assert mean.dtype == torch.float32 and std.dtype == torch.float32 and mean.numel() == 3 and std.numel() == 3
+    B, _, H, W = x.shape
+    if out is None:
+        out = torch.empty(B, 3, size, size, device=x.device, dtype=_BF16)
+    assert out.dtype == _BF16 and out.is_contiguous() and tuple(out.shape) == (B, 3, size, size)
+    rc = _lib.lib().wg_normalize_pad_bf16(x.data_ptr(), 1 if x.dtype == torch.uint8 else 0, mean.data_ptr(), std.data_ptr(), out.data_ptr(), B, H,
+                                          W, size, _stream())
+    _lib.check(rc, "wg_normalize_pad_bf16")
+    return out
+
+
 def hyper_mask_dot(up, hyper, T, h, w, first_mask, num_masks):
     """up: pixel-shuffled upscaled embedding rows [T*h*w*4, 4*32]; hyper [T, nmask, 32] -> fp32 [T, num_masks, 4h, 4w]."""
     _need_gpu(up, hyper)

@@ -306,9 +306,9 @@ class PositionEmbeddingRandom(nn.Module):
         return self.tokens(size).t().reshape(-1, h, w)
 
 
-class PromptEncoder(nn.Module):
-    """prompt_encoder.py:16-186.  Only the text branch (`text_embeds`) is on WalkGPT's path; point / box / mask prompts
-    keep their parameters (checkpoint parity) but are out of scope."""
+class PromptEncoder(nn.Module, _Prepared):
+    """prompt_encoder.py:16-186.  The text branch (`text_embeds`) is WalkGPT's path; point / box prompts run through wg_prompt_sparse_f32 and
+    mask prompts through wg_mask_embed_bf16 (inference only)."""
 
     def __init__(self, embed_dim, image_embedding_size, input_image_size, mask_in_chans, activation=nn.GELU):
         super().__init__()
@@ -346,14 +346,78 @@ class PromptEncoder(nn.Module):
         h, w = self.image_embedding_size
         return self._pe_cache[1].t().reshape(1, -1, h, w)
 
-    def forward(self, points, boxes, masks, text_embeds):
-        if points is not None or boxes is not None or masks is not None:
-            raise NotImplementedError("walkgpt_amd: only the text-embedding prompt branch is on the WalkGPT hot path")
-        if text_embeds is None:
-            raise ValueError("text_embeds is required")
-        bs = text_embeds.shape[0]
-        sparse = text_embeds  # prompt_encoder.py:175-176: concatenation with an empty tensor
-        dense = self.no_mask_embed.weight.reshape(1, -1, 1, 1).expand(bs, -1, self.image_embedding_size[0], self.image_embedding_size[1])
+    def _point_params(self):
+        return list(self.point_embeddings.parameters()) + list(self.not_a_point_embed.parameters())
+
+    def _embed_table(self):
+        """[5, C] fp32: point_embeddings[0..3], not_a_point_embed (wg_prompt_sparse_f32's table)."""
+        return self._prep_get(lambda: torch.cat([e.weight for e in self.point_embeddings] + [self.not_a_point_embed.weight], 0).float().contiguous(),
+                              self._point_params(), slot="_pts")
+
+    def _mask_params(self):
+        """mask_downscaling as the fp32 blob of wg_mask_embed_bf16 (include/walkgpt_hip.h)."""
+        m = self.mask_downscaling
+        return self._prep_get(lambda: torch.cat([t.detach().reshape(-1).float() for t in (
+            m[0].weight, m[0].bias, m[1].weight, m[1].bias, m[3].weight, m[3].bias, m[4].weight, m[4].bias, m[6].weight, m[6].bias)]).contiguous(),
+            list(m.parameters()), slot="_mask")
+
+    def _get_batch_size(self, points, boxes, masks, text_embeds):
+        if points is not None:
+            return points[0].shape[0]
+        elif boxes is not None:
+            return boxes.shape[0]
+        elif masks is not None:
+            return masks.shape[0]
+        elif text_embeds is not None:
+            return text_embeds.shape[0]
+        return 1
+
+    @staticmethod
+    def _no_grad_check(what, tensors):
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+            raise RuntimeError("walkgpt_amd: %s prompts are inference-only (no backward pass is built for them); run under torch.no_grad() "
+                               "or freeze the prompt encoder's parameters" % what)
+
+    def forward(self, points, boxes, masks, text_embeds=None):
+        """prompt_encoder.py:150-186.  text_embeds defaults to None so that upstream SAM callers (Sam.forward, SamPredictor) work unchanged."""
+        if points is None and boxes is None and masks is None:
+            if text_embeds is None:
+                raise ValueError("text_embeds is required")
+            bs = text_embeds.shape[0]
+            sparse = text_embeds  # prompt_encoder.py:175-176: concatenation with an empty tensor
+            dense = self.no_mask_embed.weight.reshape(1, -1, 1, 1).expand(bs, -1, self.image_embedding_size[0], self.image_embedding_size[1])
+            return sparse, dense
+        bs = self._get_batch_size(points, boxes, masks, text_embeds)
+        dev = self.point_embeddings[0].weight.device
+        if points is not None or boxes is not None:
+            self._no_grad_check("point / box", self._point_params() + [text_embeds])
+            coords = labels = box = None
+            if points is not None:
+                coords = points[0].to(dev, torch.float32).contiguous()
+                labels = points[1].to(dev, torch.int32).contiguous()
+            if boxes is not None:
+                box = boxes.to(dev, torch.float32).reshape(-1, 4).contiguous()
+                if box.shape[0] != bs:
+                    raise ValueError("boxes hold %d prompts, points %d" % (box.shape[0], bs))
+            text = None if text_embeds is None else text_embeds.contiguous()
+            G = self.pe_layer.positional_encoding_gaussian_matrix
+            sparse = ops.prompt_sparse(coords, labels, boxes is None, box, text, G.float().contiguous(), self._embed_table(), self.input_image_size)
+        elif text_embeds is not None:
+            sparse = text_embeds
+        else:
+            sparse = torch.empty(bs, 0, self.embed_dim, device=dev)
+        if masks is None:
+            dense = self.no_mask_embed.weight.reshape(1, -1, 1, 1).expand(bs, -1, self.image_embedding_size[0], self.image_embedding_size[1])
+            return sparse, dense
+        m = self.mask_downscaling
+        if m[0].in_channels != 1 or m[0].out_channels != 4 or m[3].out_channels != 16 or m[6].out_channels != 256:
+            raise NotImplementedError("the mask-prompt kernel is built for SAM's mask_downscaling (mask_in_chans 16, embed_dim 256)")
+        self._no_grad_check("mask", list(m.parameters()))
+        h, w = self.image_embedding_size
+        if tuple(masks.shape[-2:]) != (4 * h, 4 * w):
+            raise ValueError("mask inputs must be %dx%d (got %s)" % (4 * h, 4 * w, tuple(masks.shape)))
+        rows = ops.mask_embed(masks.to(dev, torch.float32).reshape(-1, 1, 4 * h, 4 * w).contiguous(), self._mask_params(), m[1].eps, m[4].eps)
+        dense = rows.view(-1, h, w, self.embed_dim).permute(0, 3, 1, 2)        # [B,256,h,w] in torch.channels_last: the same bytes
         return sparse, dense
 
 
@@ -833,6 +897,10 @@ class MaskDecoder(nn.Module, _Prepared):
             sl = (1, self.num_mask_tokens - 1) if multimask_output else (0, 1)
             return self.predict_masks_tokens(emb, pe, sparse_prompt_embeddings, h, w, sl,      # one image shared by all prompts
                                              src_bias=d[0, :, 0, 0].to(BF16).reshape(1, c).contiguous())
+        elif d.dtype == BF16 and d.shape[0] == P and d.is_contiguous(memory_format=torch.channels_last):
+            # per-prompt dense embedding in channels_last bf16 (PromptEncoder's mask prompts): its bytes are already token rows; the image rows are
+            # broadcast by row index modulo h*w (one image) or line up with them (one image per prompt)
+            src = ops.add_rows(d.permute(0, 2, 3, 1).reshape(P, h * w, c), emb.reshape(-1, c))
         else:
             src = ops.add_rows(emb.expand(P, -1, -1).contiguous() if b == 1 else emb,
                                ops.nchw_to_tokens(d.to(BF16).contiguous()).reshape(-1, c))
@@ -842,7 +910,7 @@ class MaskDecoder(nn.Module, _Prepared):
 
 
 class Sam(nn.Module):
-    """sam.py:18-172 container + postprocess_masks (the only method WalkGPT calls on it)."""
+    """sam.py:18-186: the container, postprocess_masks (the method WalkGPT calls), preprocess and the upstream forward()."""
 
     mask_threshold: float = 0.0
     image_format: str = "RGB"
@@ -859,6 +927,40 @@ class Sam(nn.Module):
     def postprocess_masks(self, masks, input_size, original_size):
         """sam.py:137-172 (fp32 out), fused into one pass by wg_postprocess_masks_f32."""
         return ops.postprocess_masks(masks.float().contiguous(), self.image_encoder.img_size, input_size, original_size)
+
+    @property
+    def device(self):
+        return self.pixel_mean.device
+
+    def preprocess(self, x: torch.Tensor) -> torch.Tensor:
+        """sam.py:174-186 through wg_normalize_pad_bf16: x [3,H,W] or [B,3,H,W] (uint8 or float) -> bf16 [(B,)3,S,S], the encoder's input type."""
+        single = x.dim() == 3
+        xb = x[None] if single else x
+        if xb.dtype != torch.uint8:
+            xb = xb.float()
+        S = self.image_encoder.img_size
+        out = ops.normalize_pad(xb.contiguous(), self.pixel_mean.float().reshape(3), self.pixel_std.float().reshape(3), S)
+        return out[0] if single else out
+
+    @torch.no_grad()
+    def forward(self, batched_input, multimask_output):
+        """sam.py:56-135: a list of {'image' [3,H,W] (already resized), 'original_size', and optionally 'point_coords' / 'point_labels', 'boxes',
+        'mask_inputs'} -> a list of {'masks' bool, 'iou_predictions', 'low_res_logits'}.  The encoder runs once on the stacked batch, the prompt
+        encoder and the decoder per image."""
+        S = self.image_encoder.img_size
+        images = torch.empty(len(batched_input), 3, S, S, device=self.device, dtype=BF16)
+        for i, rec in enumerate(batched_input):
+            images[i] = self.preprocess(rec["image"].to(self.device))
+        image_embeddings = self.image_encoder(images)
+        outputs = []
+        for rec, emb in zip(batched_input, image_embeddings):
+            points = (rec["point_coords"], rec["point_labels"]) if "point_coords" in rec else None
+            sparse, dense = self.prompt_encoder(points=points, boxes=rec.get("boxes", None), masks=rec.get("mask_inputs", None))
+            low_res, iou = self.mask_decoder(image_embeddings=emb.unsqueeze(0), image_pe=self.prompt_encoder.get_dense_pe(),
+                                             sparse_prompt_embeddings=sparse, dense_prompt_embeddings=dense, multimask_output=multimask_output)
+            masks = self.postprocess_masks(low_res, input_size=rec["image"].shape[-2:], original_size=rec["original_size"])
+            outputs.append({"masks": masks > self.mask_threshold, "iou_predictions": iou, "low_res_logits": low_res})
+        return outputs
 
 
 def _build_sam(encoder_embed_dim, encoder_depth, encoder_num_heads, encoder_global_attn_indexes, checkpoint=None,
