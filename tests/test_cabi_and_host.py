@@ -159,15 +159,89 @@ def test_clip_tower_resizes_a_stock_position_table_on_load():
     assert np.allclose(got, gold["table"], atol=1e-6)
 
 
-def test_tile_selector_sees_k():
-    """The kernel id host-side accounting reports is the one the library launches: M <= 16 rows take the skinny kernel (5) only when
-    K % 128 == 0; K = 192 passes the MFMA path's K % 64 rule and runs on the 128x128 tiles (1)."""
+# The GEMM queries, one row per shape: (M, N, K, lda, ldw, ldc, ldr) -> what wg_gemm_pick_tile, wg_gemm_pick_tile_ex (allow_tail 0 / 1),
+# wg_gemm_pick_tile_mnk (allow_tail 0 / 1), wg_gemm_ln_supported, wg_gemm_row_partials_supported, wg_gemm_skinny_ln_supported and
+# ops.gemm_tile_for (tail_tiles False / True) return.  Kernel ids: 1 = 128x128 tiles, 3 = row-wave, 5 = skinny, 11 = persistent 128x128,
+# 12 = 128x128 with the M % 128 <= 16 leftover rows in the last row tile, 16 = persistent 256x256.
+_E = 1 << 20
+_GEMM_QUERIES = [
+    # M <= 16: the skinny kernel when N % 16 == 0, and only at K % 128 == 0 (K = 192 takes the 128x128 tiles)
+    ((8, 256, 256, 256, 256, 256, 0), (5, 5, 5, 5, 5, 0, 0, 1, 5, 5)),
+    ((8, 256, 192, 192, 192, 256, 0), (5, 5, 5, 1, 1, 0, 0, 0, 1, 1)),
+    ((16, 4096, 4096, 4096, 4096, 4096, 0), (5, 5, 5, 5, 5, 0, 0, 1, 5, 5)),
+    ((8, 100, 256, 256, 256, 100, 0), (1, 1, 1, 1, 1, 0, 0, 0, 1, 1)),
+    ((1, 16, 128, 128, 128, 16, 0), (5, 5, 5, 5, 5, 0, 0, 1, 5, 5)),
+    ((0, 256, 256, 256, 256, 256, 0), (5, 5, 5, 5, 5, 0, 0, 0, 5, 5)),
+    ((8, 256, 256, 260, 256, 256, 0), (5, 5, 5, 5, 5, 0, 0, 0, 3, 3)),
+    ((8, 256, 256, 256, 256, 258, 0), (5, 5, 5, 5, 5, 0, 0, 0, 3, 3)),
+    # 17 <= M <= 128: 128x128 tiles, or the skinny kernel where its cost model says it wins
+    ((17, 1024, 1024, 1024, 1024, 1024, 0), (1, 1, 1, 5, 5, 0, 0, 1, 5, 5)),
+    ((32, 4096, 4096, 4096, 4096, 4096, 0), (1, 1, 1, 5, 5, 0, 0, 1, 5, 5)),
+    ((96, 1024, 1024, 1024, 1024, 1024, 0), (1, 1, 1, 5, 5, 0, 0, 1, 5, 5)),
+    ((128, 256, 5120, 5120, 5120, 256, 0), (1, 1, 1, 5, 5, 0, 0, 1, 5, 5)),
+    ((64, 256, 192, 192, 192, 256, 0), (1, 1, 1, 1, 1, 0, 0, 0, 1, 1)),
+    ((100, 4096, 4096, 4104, 4096, 4096, 4096), (1, 1, 1, 1, 1, 0, 0, 1, 1, 1)),
+    ((128, 8192, 256, 256, 256, 8192, 0), (1, 1, 1, 5, 5, 0, 0, 1, 5, 5)),
+    ((128, 16384, 256, 256, 256, 16384, 0), (1, 1, 1, 1, 1, 0, 0, 1, 1, 1)),
+    ((129, 256, 256, 256, 256, 256, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11)),
+    # M = 8 * 1025 and other M % 128 in 1..16: the tail kernel (12) only with allow_tail, N % 8 == 0, and when it fills the chip
+    ((8200, 1024, 1024, 1024, 1024, 1024, 0), (16, 16, 12, 16, 12, 1, 1, 0, 16, 12)),
+    ((8200, 3072, 1024, 1024, 1024, 3072, 0), (16, 16, 12, 16, 12, 1, 0, 0, 16, 12)),
+    ((8200, 4096, 1024, 1024, 1024, 4096, 4096), (16, 16, 12, 16, 12, 1, 0, 0, 16, 12)),
+    ((8200, 1028, 1024, 1024, 1024, 1028, 0), (16, 16, 16, 16, 16, 0, 0, 0, 16, 16)),
+    ((2050, 1024, 1024, 1024, 1024, 1024, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11)),
+    ((4112, 768, 768, 768, 768, 768, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11)),
+    ((4113, 768, 768, 768, 768, 768, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11)),
+    # N = 128 / 384 / < 256: 128x128 persistent tiles; N >= 256: 256x256 unless too few big tiles (or, with allow_tail, worse rounds)
+    ((4096, 128, 256, 256, 256, 128, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11)),
+    ((4096, 384, 768, 768, 768, 384, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11)),
+    ((4096, 192, 256, 256, 256, 192, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11)),
+    ((4096, 64, 64, 64, 64, 64, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11)),
+    ((1024, 1024, 1024, 1024, 1024, 1024, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11)),
+    ((32768, 768, 768, 768, 768, 768, 768), (16, 16, 11, 16, 11, 1, 1, 0, 16, 11)),
+    ((32768, 2304, 768, 768, 768, 2304, 0), (16, 16, 16, 16, 16, 1, 0, 0, 16, 16)),
+    ((32768, 1280, 5120, 5120, 5120, 1280, 1280), (16, 16, 16, 16, 16, 1, 1, 0, 16, 16)),
+    ((32768, 1536, 768, 768, 768, 1536, 0), (16, 16, 16, 16, 16, 1, 0, 0, 16, 16)),
+    ((32768, 1152, 768, 768, 768, 1152, 0), (16, 16, 16, 16, 16, 1, 0, 0, 16, 16)),
+    ((16384, 1536, 768, 768, 768, 1536, 0), (16, 16, 11, 16, 11, 1, 0, 0, 16, 11)),
+    # padded and odd leading dimensions, K off the MFMA path's K % 64 rule
+    ((4096, 1024, 1024, 1028, 1024, 1024, 0), (16, 16, 11, 16, 11, 0, 0, 0, 3, 3)),
+    ((4096, 1024, 1024, 1024, 1030, 1024, 0), (16, 16, 11, 16, 11, 0, 0, 0, 3, 3)),
+    ((4096, 1024, 1024, 1024, 1024, 1028, 0), (16, 16, 11, 16, 11, 0, 0, 0, 16, 11)),
+    ((4096, 1024, 1024, 1024, 1024, 1030, 0), (16, 16, 11, 16, 11, 0, 0, 0, 3, 3)),
+    ((4096, 1024, 1024, 1024, 1024, 1024, 1026), (16, 16, 11, 16, 11, 1, 1, 0, 3, 3)),
+    ((4096, 1024, 1000, 1000, 1000, 1024, 0), (16, 16, 11, 16, 11, 0, 0, 0, 3, 3)),
+    ((4096, 1024, 1024, 1536, 1152, 1280, 1032), (16, 16, 11, 16, 11, 1, 1, 0, 16, 11)),
+    # the persistent kernel's 4 GiB operand bound ((M + 256) * lda, (N + 256) * ldw below 2^31 elements) and C's 2 GiB extent
+    ((_E - 257, 1024, 2048, 2048, 2048, 1024, 0), (16, 16, 16, 16, 16, 1, 1, 0, 16, 16)),
+    ((_E - 256, 1024, 2048, 2048, 2048, 1024, 0), (16, 16, 16, 16, 16, 0, 0, 0, 16, 16)),
+    ((1000, _E - 264, 2048, 2048, 2048, _E - 264, 0), (16, 16, 16, 16, 16, 1, 0, 0, 16, 16)),
+    ((1000, _E - 256, 2048, 2048, 2048, _E - 256, 0), (16, 16, 16, 16, 16, 0, 0, 0, 16, 16)),
+    ((32768, 1024, 1024, 1024, 1024, 32768, 0), (16, 16, 16, 16, 16, 1, 1, 0, 16, 16)),
+    ((32768, 1024, 1024, 1024, 1024, 40960, 0), (16, 16, 16, 16, 16, 0, 0, 0, 16, 16)),
+]
+
+
+def _gemm_query_mismatches(columns):
     from walkgpt_amd import _lib, ops
     L = _lib.lib()
-    assert L.wg_gemm_pick_tile_ex(8, 256, 0) == 5
-    assert L.wg_gemm_pick_tile_mnk(8, 256, 256, 0) == 5 and L.wg_gemm_pick_tile_mnk(8, 256, 192, 0) == 1
-    assert L.wg_gemm_pick_tile_mnk(32768, 768, 768, 0) == L.wg_gemm_pick_tile_ex(32768, 768, 0) == 16
-    assert ops.gemm_tile_for(8, 256, 192, 192, 192, 256, 0) == 1 and ops.gemm_tile_for(8, 256, 256, 256, 256, 256, 0) == 5
+    bad = []
+    for (M, N, K, lda, ldw, ldc, ldr), want in _GEMM_QUERIES:
+        got = (L.wg_gemm_pick_tile(M, N), L.wg_gemm_pick_tile_ex(M, N, 0), L.wg_gemm_pick_tile_ex(M, N, 1),
+               L.wg_gemm_pick_tile_mnk(M, N, K, 0), L.wg_gemm_pick_tile_mnk(M, N, K, 1),
+               L.wg_gemm_ln_supported(M, N, K, lda, ldw, ldc), L.wg_gemm_row_partials_supported(M, N, K, lda, ldw, ldc),
+               L.wg_gemm_skinny_ln_supported(M, N, K, lda, ldw, ldc),
+               ops.gemm_tile_for(M, N, K, lda, ldw, ldc, ldr), ops.gemm_tile_for(M, N, K, lda, ldw, ldc, ldr, True))
+        if [got[i] for i in columns] != [want[i] for i in columns]:
+            bad.append(((M, N, K, lda, ldw, ldc, ldr), [want[i] for i in columns], [got[i] for i in columns]))
+    return bad
+
+
+def test_tile_selector_sees_k():
+    """The kernel id host-side accounting reports is the one the library launches: M <= 16 rows take the skinny kernel (5) only when
+    K % 128 == 0; K = 192 passes the MFMA path's K % 64 rule and runs on the 128x128 tiles (1).  Pinned over _GEMM_QUERIES for
+    wg_gemm_pick_tile, _ex, _mnk and ops.gemm_tile_for."""
+    assert _gemm_query_mismatches([0, 1, 2, 3, 4, 8, 9]) == []
 
 
 @pytest.mark.parametrize("name", ["w56", "w448"])
@@ -284,11 +358,82 @@ def test_epilogue_gelu_fit_is_within_its_stated_error():
 
 def test_persistent_gemm_operand_bound_is_reported_by_the_supported_queries():
     """The persistent kernel reads A and W through 32-bit buffer descriptors reaching up to 255 rows past the last one: the `supported` queries the host
-    asks before it plans a LayerNorm fold or a row-sum hand-over say no for operands that, padded to whole tiles, reach 4 GiB (pure host arithmetic)."""
+    asks before it plans a LayerNorm fold or a row-sum hand-over say no for operands that, padded to whole tiles, reach 4 GiB (pure host arithmetic).
+    Pinned over _GEMM_QUERIES for wg_gemm_ln_supported, wg_gemm_row_partials_supported and wg_gemm_skinny_ln_supported."""
+    assert _gemm_query_mismatches([5, 6, 7]) == []
+
+_P = 1 << 20   # a 16-byte aligned address: every call below is refused before it could be used
+_GEMM_ENTRY_ARGS = {   # parameter names (include/walkgpt_hip.h) and arguments every row below spoils in one place
+    "wg_gemm_bias_act_bf16": ("A lda W ldw bias residual ldr res_row_mod C ldc M N K act out_f32 tile_hint stream",
+                              (_P, 1024, _P, 1024, None, None, 0, 0, _P, 1024, 4096, 1024, 1024, 0, 0, 0, None)),
+    "wg_gemm_skinny_ln_bias_act_bf16": ("A lda gamma beta eps W ldw w_tiled bias C ldc M N K act out_f32 stream",
+                                        (_P, 256, None, None, 1e-5, _P, 256, 0, None, _P, 256, 8, 256, 256, 0, 0, None)),
+    "wg_gemm_ln_bias_act_bf16": ("A lda Wg ldw bias_f32 colsum stats C ldc M N K act stream",
+                                 (_P, 768, _P, 768, _P, _P, _P, _P, 2304, 32768, 2304, 768, 0, None)),
+    "wg_gemm_lnp_bias_act_bf16": ("A lda Wg ldw bias_f32 colsum row_partials n_partials mpad eps C ldc M N K act stream",
+                                  (_P, 768, _P, 768, _P, _P, _P, 3, 32768, 1e-5, _P, 2304, 32768, 2304, 768, 0, None)),
+    "wg_gemm_bias_act_stats_bf16": ("A lda W ldw bias residual ldr res_row_mod C ldc M N K act row_partials mpad stream",
+                                    (_P, 768, _P, 768, None, None, 0, 0, _P, 768, 32768, 768, 768, 0, _P, 32768, None)),
+    "wg_gemm_mxfp8": ("Aq lda a_mx a_pitch Wq ldw w_mx w_pitch bias ln_colsum ln_bias ln_part ln_np ln_mpad ln_eps residual ldr res_row_mod "
+                      "C ldc Cq ldcq c_mx c_pitch stats_part stats_mpad M N K act stream",
+                      (_P, 1024, _P, 4096, _P, 1024, _P, 1024, None, None, None, None, 0, 0, 0.0, None, 0, 0,
+                       _P, 1024, None, 0, None, 0, None, 0, 4096, 1024, 1024, 0, None)),
+    "wg_gemm_fp8_bias_act": ("Aq lda scale_a Wq ldw scale_w bias residual ldr res_row_mod C ldc M N K act stream",
+                             (_P, 1024, _P, _P, 1024, _P, None, None, 0, 0, _P, 1024, 4096, 1024, 1024, 0, None)),
+}
+_GEMM_REJECTS = [   # (entry point, spoiled arguments, prefix of wg_last_error())
+    ("wg_gemm_bias_act_bf16", dict(W=None), "gemm: "),
+    ("wg_gemm_bias_act_bf16", dict(M=0), "gemm: "),
+    ("wg_gemm_bias_act_bf16", dict(ldc=1000), "gemm: "),
+    ("wg_gemm_bias_act_bf16", dict(act=4), "gemm: "),
+    ("wg_gemm_bias_act_bf16", dict(residual=_P, ldr=512), "gemm: "),   # (misaligned operands are not refused: they take the row-wave kernel)
+    ("wg_gemm_skinny_ln_bias_act_bf16", dict(gamma=_P), "gemm_skinny: "),
+    ("wg_gemm_skinny_ln_bias_act_bf16", dict(gamma=_P + 8, beta=_P), "gemm_skinny: "),
+    ("wg_gemm_skinny_ln_bias_act_bf16", dict(W=_P + 8), "gemm_skinny: "),
+    ("wg_gemm_skinny_ln_bias_act_bf16", dict(M=129), "gemm_skinny: "),
+    ("wg_gemm_skinny_ln_bias_act_bf16", dict(K=192, lda=192, ldw=192), "gemm_skinny: "),
+    ("wg_gemm_skinny_ln_bias_act_bf16", dict(A=None), "gemm: "),
+    ("wg_gemm_ln_bias_act_bf16", dict(colsum=None), "gemm_ln: "),
+    ("wg_gemm_ln_bias_act_bf16", dict(stats=_P + 8), "gemm_ln: "),
+    ("wg_gemm_ln_bias_act_bf16", dict(C=_P + 8), "gemm_ln: "),
+    ("wg_gemm_ln_bias_act_bf16", dict(M=100), "gemm_ln: "),
+    ("wg_gemm_ln_bias_act_bf16", dict(ldc=2300), "gemm_ln: "),
+    ("wg_gemm_lnp_bias_act_bf16", dict(row_partials=None), "gemm_lnp: "),
+    ("wg_gemm_lnp_bias_act_bf16", dict(bias_f32=_P + 4), "gemm_lnp: "),
+    ("wg_gemm_lnp_bias_act_bf16", dict(n_partials=2), "gemm_lnp: "),
+    ("wg_gemm_lnp_bias_act_bf16", dict(mpad=32000), "gemm_lnp: "),
+    ("wg_gemm_lnp_bias_act_bf16", dict(M=100, mpad=256), "gemm_lnp: "),
+    ("wg_gemm_bias_act_stats_bf16", dict(row_partials=None), "gemm_stats: "),
+    ("wg_gemm_bias_act_stats_bf16", dict(bias=_P + 8), "gemm_stats: "),
+    ("wg_gemm_bias_act_stats_bf16", dict(N=1536, ldc=1536), "gemm_stats: "),
+    ("wg_gemm_bias_act_stats_bf16", dict(mpad=32000), "gemm_stats: "),
+    # a residual spanning 2 GiB or more cannot take the staged epilogue the row partials need
+    ("wg_gemm_bias_act_stats_bf16", dict(residual=_P, ldr=1 << 20), "gemm: "),
+    ("wg_gemm_mxfp8", dict(w_mx=None), "gemm_mxfp8: "),
+    ("wg_gemm_mxfp8", dict(Aq=_P + 8), "gemm_mxfp8: "),
+    ("wg_gemm_mxfp8", dict(K=192, lda=192, ldw=192), "gemm_mxfp8: "),
+    ("wg_gemm_mxfp8", dict(ldc=1 << 20), "gemm_mxfp8: "),
+    ("wg_gemm_mxfp8", dict(residual=_P, ldr=1 << 20), "gemm_mxfp8: "),
+    ("wg_gemm_mxfp8", dict(Cq=_P, ldcq=1 << 20, c_mx=_P, c_pitch=4096), "gemm_mxfp8: "),
+    ("wg_gemm_fp8_bias_act", dict(scale_w=None), "gemm_fp8: "),
+    ("wg_gemm_fp8_bias_act", dict(bias=_P + 4), "gemm_fp8: "),
+    ("wg_gemm_fp8_bias_act", dict(N=1004), "gemm_fp8: "),
+    ("wg_gemm_fp8_bias_act", dict(ldc=1 << 20), "gemm_fp8: "),
+]
+
+
+def test_gemm_entry_points_refuse_bad_arguments_before_any_hip_call():
+    """Every GEMM entry point refuses a null operand, a misaligned pointer and a shape it does not take with WG_ERR_BAD_ARG, before it
+    touches the device, and names itself in wg_last_error()."""
     from walkgpt_amd import _lib
     L = _lib.lib()
-    assert L.wg_gemm_ln_supported(32768, 2304, 768, 768, 768, 2304) == 1
-    assert L.wg_gemm_ln_supported((1 << 20) - 256 - 1, 1024, 2048, 2048, 2048, 1024) == 1        # (M + 256) * lda just under 2^31
-    assert L.wg_gemm_ln_supported((1 << 20) - 256, 1024, 2048, 2048, 2048, 1024) == 0
-    assert L.wg_gemm_row_partials_supported((1 << 20) - 256, 1024, 2048, 2048, 2048, 1024) == 0
-
+    bad = []
+    for entry, spoil, prefix in _GEMM_REJECTS:
+        names, base = _GEMM_ENTRY_ARGS[entry]
+        names = names.split()
+        assert set(spoil) <= set(names) and len(names) == len(base)
+        rc = getattr(L, entry)(*[spoil.get(n, v) for n, v in zip(names, base)])
+        msg = L.wg_last_error().decode()
+        if rc != -1 or not msg.startswith(prefix):
+            bad.append((entry, spoil, rc, msg))
+    assert bad == []

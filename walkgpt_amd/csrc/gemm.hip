@@ -1713,14 +1713,20 @@ __global__ __launch_bounds__(512, 2) void wg_gemm_pp_persist_kernel(GemmArgs g) 
     }
 }
 
-// The persistent kernel addresses A and W through 32-bit buffer offsets that reach up to 255 rows past the last one (those read as zero): both
-// operands, padded to whole tiles, must stay below 4 GiB.
-static bool wg_pp_operands_ok(int M, int N, long lda, long ldw) {
-    return (long)(M + 256) * lda < (1L << 31) && (long)(N + 256) * ldw < (1L << 31);
+// The persistent kernels address A and W through 32-bit buffer offsets; the 256x256 one reaches up to 255 rows past the last one (those read
+// as zero): both operands, `pad` rows longer, must stay below 4 GiB.
+static bool wg_operands_fit(const GemmArgs& g, int pad) {
+    return (long)(g.M + pad) * g.lda < (1L << 31) && (long)(g.N + pad) * g.ldw < (1L << 31);
+}
+
+// The staged (LDS-transposed, 16-byte) epilogue: bf16 outputs whose rows are 16-byte addressable, C (and R) within 32-bit byte offsets.
+static bool wg_staged_ok(const GemmArgs& g) {
+    return !g.out_f32 && g.N % 8 == 0 && g.ldc % 8 == 0 && g.c_bytes != 0 &&
+           (!g.R || (g.ldr % 8 == 0 && ((uintptr_t)g.R & 15) == 0 && g.r_bytes != 0));
 }
 
 static int launch_pp_persist(GemmArgs& g, hipStream_t st) {
-    WG_REQUIRE(wg_pp_operands_ok(g.M, g.N, g.lda, g.ldw), "persistent gemm: an operand (padded to whole 256-row tiles) is larger than 4 GiB");
+    WG_REQUIRE(wg_operands_fit(g, 256), "persistent gemm: an operand (padded to whole 256-row tiles) is larger than 4 GiB");
     g.tiles_m = (g.M + 255) / 256;
     g.tiles_n = (g.N + 255) / 256;
     g.a_bytes = (unsigned)(((long)(g.M - 1) * g.lda + g.K) * 2);
@@ -1783,12 +1789,14 @@ static int launch_pp_persist(GemmArgs& g, hipStream_t st) {
 
 template <int BM, int BN, int BK, int STAGES, int WM, int WN, int PIPE = 0>
 static int launch_tile(GemmArgs& g, hipStream_t st) {
-    // staged (LDS-transposed, 16-byte) epilogue for bf16 outputs whose rows are 16-byte addressable
-    const bool staged = !g.out_f32 && g.N % 8 == 0 && g.ldc % 8 == 0 && g.c_bytes != 0 &&
-                        (!g.R || (g.ldr % 8 == 0 && ((uintptr_t)g.R & 15) == 0 && g.r_bytes != 0));
-    return staged ? launch_tile_impl<BM, BN, BK, STAGES, WM, WN, true, PIPE>(g, st)
-                  : launch_tile_impl<BM, BN, BK, STAGES, WM, WN, false, PIPE>(g, st);
+    return wg_staged_ok(g) ? launch_tile_impl<BM, BN, BK, STAGES, WM, WN, true, PIPE>(g, st)
+                           : launch_tile_impl<BM, BN, BK, STAGES, WM, WN, false, PIPE>(g, st);
 }
+
+// The skinny kernel's shape: a few rows, whole 16-column blocks, K in whole 128-deep steps (32 per wave, 4 or 16 waves).
+static bool wg_skinny_shape(int M, int N, int K) { return M <= 128 && N % 16 == 0 && K % 128 == 0; }
+// M just above a multiple of 128: the tail kernel's last row tile absorbs the M % 128 <= 16 leftover rows.
+static bool wg_tail_rows(int M) { return M >= 128 && M % 128 >= 1 && M % 128 <= 16; }
 
 // Tile choice (measured, tools/bench_gemm.py and bench.py with WG_GEMM_TILE=n on MI355X): the 256x256 kernel
 // (8 waves, 1 workgroup / CU) is ~15 % better per tile-slot than the 128x128 one, and with the CLIP tower and the SAM
@@ -1802,7 +1810,7 @@ static int launch_tile(GemmArgs& g, hipStream_t st) {
 extern "C" int wg_gemm_pick_tile_ex(int M, int N, int allow_tail) {
     if (M <= 16 && N % 16 == 0) return 5;   // a handful of rows: weight streaming spread over N / 16 workgroups (needs K % 128 == 0)
     if (M <= 128) return 1;             // decoder token-side linears: one or two workgroups
-    if (allow_tail && M % 128 >= 1 && M % 128 <= 16 && N % 8 == 0) {
+    if (allow_tail && wg_tail_rows(M) && N % 8 == 0) {
         // ragged M just above a multiple of 128 (CLIP: 8 * 1025): fold the leftover rows into the last row tile when that
         // removes a nearly empty round of 128x128 tiles and the big tiles would not fill the chip well either
         const long t = (long)(M / 128) * ((N + 127) / 128);
@@ -1837,7 +1845,7 @@ extern "C" int wg_gemm_pick_tile(int M, int N) { return wg_gemm_pick_tile_ex(M, 
 // columns and walk K in a single chain (14 us at K = 1024, 40 us at K = 4096, whatever M <= 128 is); the skinny kernel spreads the same
 // weights over (M / 16) x (N / 16) workgroups: 5 us + ~6.6 ns per workgroup and 1024 of K (tools/micro/skinny_bench.py under rocprofv3).
 static bool wg_skinny_wins(int M, int N, int K) {
-    if (M > 128 || N % 16 != 0 || K % 128 != 0) return false;
+    if (!wg_skinny_shape(M, N, K)) return false;
     const double kk = K / 1024.0;
     const double blocks = (double)((M + 15) / 16) * (N / 16);
     return 4.5 + (K >= 2048 ? 5.0 : 0.0) + blocks * kk * 0.0066 < 14.0 * (kk < 1.0 ? 1.0 : kk);
@@ -1845,151 +1853,71 @@ static bool wg_skinny_wins(int M, int N, int K) {
 extern "C" int wg_gemm_pick_tile_mnk(int M, int N, int K, int allow_tail) {
     const int t = wg_gemm_pick_tile_ex(M, N, allow_tail);
     if (t == 1 && wg_skinny_wins(M, N, K)) return 5;
-    return (t == 5 && K % 128 != 0) ? 1 : t;
+    return (t == 5 && !wg_skinny_shape(M, N, K)) ? 1 : t;
 }
 
-struct GemmStatsIO {   // row statistics travelling between two persistent GEMMs (see wg_gemm_pp_persist_kernel)
-    const float* ln_part = nullptr; int ln_np = 0; long ln_mpad = 0; float ln_eps = 0.f;   // consumer
-    float* stats_part = nullptr; long stats_mpad = 0;                                      // producer
-};
-static int wg_gemm_dispatch(const void* A, long lda, const void* W, long ldw, const void* bias, const void* residual, long ldr,
-                            int res_row_mod, void* C, long ldc, int M, int N, int K, int act, int out_f32, int tile_hint,
-                            const float* ln_stats, const float* ln_s, const float* ln_b, void* stream, const bf16* sk_gamma = nullptr,
-                            const bf16* sk_beta = nullptr, float sk_eps = 0.f, int sk_tiled = 0, const GemmStatsIO* sio = nullptr);
-
-extern "C" int wg_gemm_bias_act_bf16(const void* A, long lda, const void* W, long ldw, const void* bias,
-                                     const void* residual, long ldr, int res_row_mod, void* C, long ldc, int M, int N,
-                                     int K, int act, int out_f32, int tile_hint, void* stream) {
-    return wg_gemm_dispatch(A, lda, W, ldw, bias, residual, ldr, res_row_mod, C, ldc, M, N, K, act, out_f32, tile_hint, nullptr, nullptr,
-                            nullptr, stream);
+// Operands the MFMA kernels take: whole 64-deep K steps, 16-byte aligned rows of A and W, C and R in 4-column groups.
+static bool wg_mfma_ok(const GemmArgs& g) {
+    return g.K % 64 == 0 && g.N % 4 == 0 && g.N >= 16 && g.lda % 8 == 0 && g.ldw % 8 == 0 && g.ldc % 4 == 0 && (!g.R || g.ldr % 4 == 0) &&
+           (((uintptr_t)g.A | (uintptr_t)g.W | (uintptr_t)g.C) & 15) == 0 && (((uintptr_t)g.bias | (uintptr_t)g.R) & 7) == 0;
 }
 
-// Skinny rows, optionally with the LayerNorm in front and / or the weight matrix in fragment order:
-//     C = act(LN?(A; gamma, beta, eps) . W^T + b)  for M <= 128, N % 16 == 0, K % 128 == 0       (text_hidden_fcs[0], utils_walkgpt.py:321-323)
-// gamma == beta == null: no LayerNorm.  w_tiled: W was re-laid by wg_tile_weight_bf16 (ldw ignored).  wg_gemm_skinny_ln_supported() tells the
-// caller whether the shape qualifies.
-extern "C" int wg_gemm_skinny_ln_supported(int M, int N, int K, long lda, long ldw, long ldc) {
-    return (M >= 1 && M <= 128 && N % 16 == 0 && K % 128 == 0 && lda % 8 == 0 && ldw % 8 == 0 && ldc % 4 == 0) ? 1 : 0;
-}
-extern "C" int wg_gemm_skinny_ln_bias_act_bf16(const void* A, long lda, const void* gamma, const void* beta, float eps, const void* W, long ldw,
-                                               int w_tiled, const void* bias, void* C, long ldc, int M, int N, int K, int act, int out_f32,
-                                               void* stream) {
-    WG_REQUIRE((gamma != nullptr) == (beta != nullptr) && (((uintptr_t)gamma | (uintptr_t)beta) & 15) == 0, "gemm_skinny: LayerNorm operands");
-    WG_REQUIRE(wg_gemm_skinny_ln_supported(M, N, K, lda, w_tiled ? 8 : ldw, ldc) && (((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) & 15) == 0,
-               "gemm_skinny: shape M=%d N=%d K=%d is not a skinny one", M, N, K);
-    return wg_gemm_dispatch(A, lda, W, w_tiled ? K : ldw, bias, nullptr, 0, 0, C, ldc, M, N, K, act, out_f32, 5, nullptr, nullptr, nullptr, stream,
-                            (const bf16*)gamma, (const bf16*)beta, eps, w_tiled);
-}
-
-// C = act(LayerNorm(A) . W^T + b) with the LayerNorm folded in: A = the raw rows, Wg = W * gamma (bf16), colsum[n] = sum_k Wg[n,k],
-// bias_f32[n] = b[n] + sum_k W[n,k] beta[k], stats[m] = {mean, rstd} of row m of A (wg_row_stats_bf16; the buffer must hold
-// M rounded up to an even number of rows, 16-byte aligned: rows travel to LDS in pairs).  Runs on the persistent
-// 256x256 kernel only: wg_gemm_ln_supported() tells the caller whether this shape / alignment qualifies.
-extern "C" int wg_gemm_ln_supported(int M, int N, int K, long lda, long ldw, long ldc) {
-    return (wg_gemm_pick_tile(M, N) == 16 && K % 64 == 0 && N % 8 == 0 && lda % 8 == 0 && ldw % 8 == 0 && ldc % 8 == 0 &&
-            (long)(M + 256) * lda < (1L << 31) && (long)(N + 256) * ldw < (1L << 31) && ((long)(M - 1) * ldc + N) * 2 < (1L << 31)) ? 1 : 0;      // (operands: wg_pp_operands_ok)
-}
-extern "C" int wg_gemm_ln_bias_act_bf16(const void* A, long lda, const void* Wg, long ldw, const float* bias_f32, const float* colsum,
-                                        const float* stats, void* C, long ldc, int M, int N, int K, int act, void* stream) {
-    WG_REQUIRE(bias_f32 && colsum && stats, "gemm_ln: null operand");
-    WG_REQUIRE((((uintptr_t)bias_f32 | (uintptr_t)colsum) & 15) == 0 && ((uintptr_t)stats & 15) == 0, "gemm_ln: misaligned operand");
-    WG_REQUIRE(wg_gemm_ln_supported(M, N, K, lda, ldw, ldc) && ((uintptr_t)C & 15) == 0, "gemm_ln: shape M=%d N=%d K=%d does not run on the persistent 256x256 kernel", M, N, K);
-    return wg_gemm_dispatch(A, lda, Wg, ldw, nullptr, nullptr, 0, 0, C, ldc, M, N, K, act, 0, 16, stats, colsum, bias_f32, stream);
+// The kernel a bf16 call runs: 3 = row-wave, 1 = 128x128 tiles, 2 = 256x256 tiles, 5 = skinny, 11 = persistent 128x128, 12 = 128x128 with the
+// leftover rows in the last row tile, 14 = 256x256 ping-pong, 16 = the same loop, persistent.  tile_hint <= 0: wg_gemm_pick_tile_mnk; a kernel
+// that cannot take these operands gives way to the 128x128 tiles (16: to 14), and so does an unknown hint.
+static int wg_gemm_route(const GemmArgs& g, int tile_hint) {
+    if (!wg_mfma_ok(g) || tile_hint == 3) return 3;
+    switch (tile_hint > 0 ? tile_hint : wg_gemm_pick_tile_mnk(g.M, g.N, g.K, 0)) {
+        case 2: return 2;
+        case 5: return wg_skinny_shape(g.M, g.N, g.K) ? 5 : 1;
+        case 11: return wg_staged_ok(g) && wg_operands_fit(g, 0) ? 11 : 1;
+        case 12: return wg_staged_ok(g) && wg_tail_rows(g.M) ? 12 : 1;
+        case 14: return 14;
+        case 16: return wg_staged_ok(g) && wg_operands_fit(g, 256) && ((uintptr_t)g.bias & 15) == 0 ? 16 : 14;
+        default: return 1;
+    }
 }
 
-// The producing side of the row statistics: wg_gemm_bias_act_bf16 that also leaves, for a later LayerNorm over its output rows,
-// row_partials[tile column][mpad][2] = {sum, sum of squares} (fp32) of the bf16 values it stored, per row and 256-column tile
-// (mpad = M rounded up to 256; N / 256 planes).  Replaces the wg_row_stats_bf16 pass in front of wg_gemm_ln_bias_act_bf16
-// (SAM: image_encoder.py:177-178,191 norm1 / norm2 behind lin2 / proj; CLIP: layer_norm1 / 2 behind fc2 / out_proj).
-// Shapes: the persistent 256x256 kernel with N % 256 == 0 (wg_gemm_row_partials_supported).
-extern "C" int wg_gemm_row_partials_supported(int M, int N, int K, long lda, long ldw, long ldc) {
-    return (wg_gemm_ln_supported(M, N, K, lda, ldw, ldc) && N % 256 == 0 && N <= 1280 &&
-            ((long)(N / 256) * (long)((M + 255) / 256 * 256) * 8 < (1L << 31))) ? 1 : 0;
-}
-extern "C" int wg_gemm_bias_act_stats_bf16(const void* A, long lda, const void* W, long ldw, const void* bias, const void* residual, long ldr,
-                                           int res_row_mod, void* C, long ldc, int M, int N, int K, int act, float* row_partials, long mpad,
-                                           void* stream) {
-    WG_REQUIRE(row_partials && ((uintptr_t)row_partials & 15) == 0, "gemm_stats: row_partials must be a 16-byte aligned buffer");
-    WG_REQUIRE(mpad % 256 == 0 && mpad >= M, "gemm_stats: mpad = %ld must be M = %d rounded up to a multiple of 256", mpad, M);
-    WG_REQUIRE(wg_gemm_row_partials_supported(M, N, K, lda, ldw, ldc) && ((uintptr_t)C & 15) == 0 && (!bias || ((uintptr_t)bias & 15) == 0) &&
-                   (!residual || (ldr % 8 == 0 && ((uintptr_t)residual & 15) == 0)),
-               "gemm_stats: shape M=%d N=%d K=%d does not run on the persistent 256x256 kernel with whole column tiles", M, N, K);
-    GemmStatsIO sio;
-    sio.stats_part = row_partials; sio.stats_mpad = mpad;
-    return wg_gemm_dispatch(A, lda, W, ldw, bias, residual, ldr, res_row_mod, C, ldc, M, N, K, act, 0, 16, nullptr, nullptr, nullptr, stream,
-                            nullptr, nullptr, 0.f, 0, &sio);
-}
-// The consuming side: wg_gemm_ln_bias_act_bf16 with the statistics given as the producer's partial sums (n_partials planes of mpad
-// rows; n_partials * 256 = K = the LayerNorm width, n_partials <= 5).  eps: the LayerNorm's.
-extern "C" int wg_gemm_lnp_bias_act_bf16(const void* A, long lda, const void* Wg, long ldw, const float* bias_f32, const float* colsum,
-                                         const float* row_partials, int n_partials, long mpad, float eps, void* C, long ldc, int M, int N, int K,
-                                         int act, void* stream) {
-    WG_REQUIRE(bias_f32 && colsum && row_partials, "gemm_lnp: null operand");
-    WG_REQUIRE((((uintptr_t)bias_f32 | (uintptr_t)colsum | (uintptr_t)row_partials) & 15) == 0, "gemm_lnp: misaligned operand");
-    WG_REQUIRE(n_partials >= 1 && n_partials <= 5 && n_partials * 256 == K, "gemm_lnp: %d partial planes do not cover K = %d", n_partials, K);
-    WG_REQUIRE(mpad % 256 == 0 && mpad >= M, "gemm_lnp: mpad = %ld must be M = %d rounded up to a multiple of 256", mpad, M);
-    WG_REQUIRE(wg_gemm_ln_supported(M, N, K, lda, ldw, ldc) && ((uintptr_t)C & 15) == 0, "gemm_lnp: shape M=%d N=%d K=%d does not run on the persistent 256x256 kernel", M, N, K);
-    GemmStatsIO sio;
-    sio.ln_part = row_partials; sio.ln_np = n_partials; sio.ln_mpad = mpad; sio.ln_eps = eps;
-    return wg_gemm_dispatch(A, lda, Wg, ldw, nullptr, nullptr, 0, 0, C, ldc, M, N, K, act, 0, 16, nullptr, colsum, bias_f32, stream,
-                            nullptr, nullptr, 0.f, 0, &sio);
+// Byte extents of C, R, Cq and Cq's block scales, which the epilogues address with 32-bit buffer offsets: one of 2 GiB or more is left 0 (not
+// addressable).  Returns whether every operand present fits.
+static bool wg_gemm_extents(GemmArgs& g) {
+    auto bytes32 = [](long b) { return b < (1L << 31) ? (unsigned)b : 0u; };
+    const long rrows = g.res_mod > 0 && g.res_mod < g.M ? g.res_mod : g.M;   // the rows of R that are read
+    g.c_bytes = g.C ? bytes32(((long)(g.M - 1) * g.ldc + g.N) * 2) : 0;
+    g.r_bytes = g.R ? bytes32(((rrows - 1) * g.ldr + g.N) * 2) : 0;
+    g.cq_bytes = g.Cq ? bytes32((long)(g.M - 1) * g.ldcq + g.N) : 0;
+    g.mx_c_bytes = g.Cq ? bytes32((long)(g.N / 32) * g.mx_c_pitch) : 0;
+    return (!g.C || g.c_bytes) && (!g.R || g.r_bytes) && (!g.Cq || (g.cq_bytes && g.mx_c_bytes));
 }
 
-static int wg_gemm_dispatch(const void* A, long lda, const void* W, long ldw, const void* bias, const void* residual, long ldr,
-                            int res_row_mod, void* C, long ldc, int M, int N, int K, int act, int out_f32, int tile_hint,
-                            const float* ln_stats, const float* ln_s, const float* ln_b, void* stream, const bf16* sk_gamma,
-                            const bf16* sk_beta, float sk_eps, int sk_tiled, const GemmStatsIO* sio) {
-    WG_REQUIRE(A && W && C, "gemm: null operand");
-    WG_REQUIRE(M > 0 && N > 0 && K > 0, "gemm: bad shape M=%d N=%d K=%d", M, N, K);
-    WG_REQUIRE(act >= 0 && act <= 3, "gemm: bad activation %d", act);
-    WG_REQUIRE(lda >= K && ldw >= K && ldc >= N, "gemm: leading dimension smaller than the row");
-    WG_REQUIRE(!residual || ldr >= N, "gemm: residual leading dimension smaller than N");
+// The operands every entry point has: C = act(A W^T ...).
+static GemmArgs wg_gemm_args(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, int act) {
     GemmArgs g;
     g.A = (const bf16*)A; g.lda = lda; g.W = (const bf16*)W; g.ldw = ldw;
-    g.bias = (const bf16*)bias; g.R = (const bf16*)residual; g.ldr = ldr; g.res_mod = res_row_mod;
-    g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.act = act; g.out_f32 = out_f32;
-    g.tiles_m = g.tiles_n = 0;
-    g.col_block = 0;
-    g.ln_stats = ln_stats; g.ln_s = ln_s; g.ln_b = ln_b;
-    g.ln_part = sio ? sio->ln_part : nullptr; g.ln_np = sio ? sio->ln_np : 0; g.ln_mpad = sio ? sio->ln_mpad : 0; g.ln_eps = sio ? sio->ln_eps : 0.f;
-    g.stats_part = sio ? sio->stats_part : nullptr; g.stats_mpad = sio ? sio->stats_mpad : 0;
-    g.scale_a = g.scale_w = nullptr;
-    g.sk_gamma = sk_gamma; g.sk_beta = sk_beta; g.sk_eps = sk_eps; g.sk_tiled = sk_tiled;
-    {   // byte extents for the staged epilogue's buffer descriptors (it addresses C and R with 32-bit byte offsets)
-        const long cb = ((long)(M - 1) * ldc + N) * 2;
-        const long rrows = res_row_mod > 0 ? (res_row_mod < M ? res_row_mod : M) : M;
-        const long rb = residual ? ((rrows - 1) * ldr + N) * 2 : 0;
-        g.c_bytes = cb < (1L << 31) ? (unsigned)cb : 0;
-        g.r_bytes = rb < (1L << 31) ? (unsigned)rb : 0;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const bool mfma_ok = (K % 64 == 0) && (N % 4 == 0) && (lda % 8 == 0) && (ldw % 8 == 0) && (ldc % 4 == 0) &&
-                         (!residual || ldr % 4 == 0) && (((uintptr_t)A | (uintptr_t)W) % 16 == 0) &&
-                         ((uintptr_t)C % 16 == 0) && (!bias || (uintptr_t)bias % 8 == 0) &&
-                         (!residual || (uintptr_t)residual % 8 == 0) && N >= 16;
-    if (!mfma_ok || tile_hint == 3) {
-        hipLaunchKernelGGL(wg_gemm_rowwave_kernel, dim3((M + 3) / 4), dim3(256), 0, st, g);
-        return wg_check_launch("wg_gemm_bias_act_bf16(rowwave)");
-    }
-    int tile = tile_hint;
-    if (tile <= 0) tile = wg_gemm_pick_tile_mnk(M, N, K, 0);
-    const bool can_stage = !out_f32 && N % 8 == 0 && ldc % 8 == 0 && g.c_bytes != 0 &&
-                           (!residual || (ldr % 8 == 0 && ((uintptr_t)residual & 15) == 0 && g.r_bytes != 0));
-    const bool small_ops = (long)M * lda < (1L << 31) && (long)N * ldw < (1L << 31);
-    if (tile == 11 && !(can_stage && small_ops)) tile = 1;
-    if (tile == 16 && !(can_stage && small_ops && wg_pp_operands_ok(M, N, lda, ldw) && (!bias || ((uintptr_t)bias % 16 == 0 && N % 8 == 0)))) {
-        WG_REQUIRE(!(g.ln_part || g.stats_part || g.ln_stats), "gemm: this operand layout cannot take the persistent kernel's staged epilogue");
-        tile = 14;
-    }
-    if (tile == 5 && !(M <= 128 && N % 16 == 0 && K % 128 == 0)) tile = 1;
-    if (tile != 1 && tile != 2 && tile != 5 && tile != 11 && tile != 12 && tile != 14 && tile != 16) tile = 1;
-    if (tile == 12 && !(can_stage && M >= 128 && M % 128 >= 1 && M % 128 <= 16)) tile = 1;
+    g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.act = act;
+    return g;
+}
+
+// The bf16 entry points' common checks, then the kernel wg_gemm_route picks.
+static int wg_gemm_launch(GemmArgs& g, int tile_hint, hipStream_t st) {
+    WG_REQUIRE(g.A && g.W && g.C, "gemm: null operand");
+    WG_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0, "gemm: bad shape M=%d N=%d K=%d", g.M, g.N, g.K);
+    WG_REQUIRE(g.act >= 0 && g.act <= 3, "gemm: bad activation %d", g.act);
+    WG_REQUIRE(g.lda >= g.K && g.ldw >= g.K && g.ldc >= g.N, "gemm: leading dimension smaller than the row");
+    WG_REQUIRE(!g.R || g.ldr >= g.N, "gemm: residual leading dimension smaller than N");
+    wg_gemm_extents(g);
+    const int tile = wg_gemm_route(g, tile_hint);
+    // (the row statistics' producer and consumers are epilogues of kernel 16; 14 is where a call asking for 16 lands otherwise)
+    WG_REQUIRE(tile != 14 || !(g.ln_part || g.stats_part || g.ln_stats), "gemm: this operand layout cannot take the persistent kernel's staged epilogue");
     switch (tile) {
+        case 3:
+            hipLaunchKernelGGL(wg_gemm_rowwave_kernel, dim3((g.M + 3) / 4), dim3(256), 0, st, g);
+            return wg_check_launch("wg_gemm_bias_act_bf16(rowwave)");
         case 5:
             {
-                const bool wide = K >= 2048 && K % 512 == 0;
+                const bool wide = g.K >= 2048 && g.K % 512 == 0;
                 const int variant = (wide ? 4 : 0) | (g.sk_gamma ? 2 : 0) | (g.sk_tiled ? 1 : 0);
-                const dim3 grid(N / 16, (M + 15) / 16), blk(wide ? 1024 : 256);
+                const dim3 grid(g.N / 16, (g.M + 15) / 16), blk(wide ? 1024 : 256);
                 switch (variant) {
                     case 0: hipLaunchKernelGGL((wg_gemm_skinny_kernel<4, false, false>), grid, blk, 0, st, g); break;
                     case 1: hipLaunchKernelGGL((wg_gemm_skinny_kernel<4, false, true>), grid, blk, 0, st, g); break;
@@ -2011,6 +1939,91 @@ static int wg_gemm_dispatch(const void* A, long lda, const void* W, long ldw, co
     }
 }
 
+extern "C" int wg_gemm_bias_act_bf16(const void* A, long lda, const void* W, long ldw, const void* bias,
+                                     const void* residual, long ldr, int res_row_mod, void* C, long ldc, int M, int N,
+                                     int K, int act, int out_f32, int tile_hint, void* stream) {
+    GemmArgs g = wg_gemm_args(A, lda, W, ldw, C, ldc, M, N, K, act);
+    g.bias = (const bf16*)bias; g.R = (const bf16*)residual; g.ldr = ldr; g.res_mod = res_row_mod; g.out_f32 = out_f32;
+    return wg_gemm_launch(g, tile_hint, (hipStream_t)stream);
+}
+
+// Skinny rows, optionally with the LayerNorm in front and / or the weight matrix in fragment order:
+//     C = act(LN?(A; gamma, beta, eps) . W^T + b)  for M <= 128, N % 16 == 0, K % 128 == 0       (text_hidden_fcs[0], utils_walkgpt.py:321-323)
+// gamma == beta == null: no LayerNorm.  w_tiled: W was re-laid by wg_tile_weight_bf16 (ldw ignored).  wg_gemm_skinny_ln_supported() tells the
+// caller whether the shape qualifies.
+extern "C" int wg_gemm_skinny_ln_supported(int M, int N, int K, long lda, long ldw, long ldc) {
+    return (M >= 1 && wg_skinny_shape(M, N, K) && lda % 8 == 0 && ldw % 8 == 0 && ldc % 4 == 0) ? 1 : 0;
+}
+extern "C" int wg_gemm_skinny_ln_bias_act_bf16(const void* A, long lda, const void* gamma, const void* beta, float eps, const void* W, long ldw,
+                                               int w_tiled, const void* bias, void* C, long ldc, int M, int N, int K, int act, int out_f32,
+                                               void* stream) {
+    WG_REQUIRE((gamma != nullptr) == (beta != nullptr) && (((uintptr_t)gamma | (uintptr_t)beta) & 15) == 0, "gemm_skinny: LayerNorm operands");
+    WG_REQUIRE(wg_gemm_skinny_ln_supported(M, N, K, lda, w_tiled ? 8 : ldw, ldc) && (((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) & 15) == 0,
+               "gemm_skinny: shape M=%d N=%d K=%d is not a skinny one", M, N, K);
+    GemmArgs g = wg_gemm_args(A, lda, W, w_tiled ? K : ldw, C, ldc, M, N, K, act);
+    g.bias = (const bf16*)bias; g.out_f32 = out_f32;
+    g.sk_gamma = (const bf16*)gamma; g.sk_beta = (const bf16*)beta; g.sk_eps = eps; g.sk_tiled = w_tiled;
+    return wg_gemm_launch(g, 5, (hipStream_t)stream);
+}
+
+// C = act(LayerNorm(A) . W^T + b) with the LayerNorm folded in: A = the raw rows, Wg = W * gamma (bf16), colsum[n] = sum_k Wg[n,k],
+// bias_f32[n] = b[n] + sum_k W[n,k] beta[k], stats[m] = {mean, rstd} of row m of A (wg_row_stats_bf16; the buffer must hold
+// M rounded up to an even number of rows, 16-byte aligned: rows travel to LDS in pairs).  Runs on the persistent
+// 256x256 kernel only: wg_gemm_ln_supported() tells the caller whether this shape / alignment qualifies -- whether the shape heuristic
+// picks that kernel and a call of this shape with 16-byte aligned operands is routed to it.
+extern "C" int wg_gemm_ln_supported(int M, int N, int K, long lda, long ldw, long ldc) {
+    if (wg_gemm_pick_tile(M, N) != 16) return 0;
+    alignas(16) static char aligned[16];   // stands for A, W and C: only their alignment is looked at
+    GemmArgs g = wg_gemm_args(aligned, lda, aligned, ldw, aligned, ldc, M, N, K, 0);
+    wg_gemm_extents(g);
+    return wg_gemm_route(g, 16) == 16 ? 1 : 0;
+}
+extern "C" int wg_gemm_ln_bias_act_bf16(const void* A, long lda, const void* Wg, long ldw, const float* bias_f32, const float* colsum,
+                                        const float* stats, void* C, long ldc, int M, int N, int K, int act, void* stream) {
+    WG_REQUIRE(bias_f32 && colsum && stats, "gemm_ln: null operand");
+    WG_REQUIRE((((uintptr_t)bias_f32 | (uintptr_t)colsum) & 15) == 0 && ((uintptr_t)stats & 15) == 0, "gemm_ln: misaligned operand");
+    WG_REQUIRE(wg_gemm_ln_supported(M, N, K, lda, ldw, ldc) && ((uintptr_t)C & 15) == 0, "gemm_ln: shape M=%d N=%d K=%d does not run on the persistent 256x256 kernel", M, N, K);
+    GemmArgs g = wg_gemm_args(A, lda, Wg, ldw, C, ldc, M, N, K, act);
+    g.ln_stats = stats; g.ln_s = colsum; g.ln_b = bias_f32;
+    return wg_gemm_launch(g, 16, (hipStream_t)stream);
+}
+
+// The producing side of the row statistics: wg_gemm_bias_act_bf16 that also leaves, for a later LayerNorm over its output rows,
+// row_partials[tile column][mpad][2] = {sum, sum of squares} (fp32) of the bf16 values it stored, per row and 256-column tile
+// (mpad = M rounded up to 256; N / 256 planes).  Replaces the wg_row_stats_bf16 pass in front of wg_gemm_ln_bias_act_bf16
+// (SAM: image_encoder.py:177-178,191 norm1 / norm2 behind lin2 / proj; CLIP: layer_norm1 / 2 behind fc2 / out_proj).
+// Shapes: the persistent 256x256 kernel with N % 256 == 0 (wg_gemm_row_partials_supported).
+extern "C" int wg_gemm_row_partials_supported(int M, int N, int K, long lda, long ldw, long ldc) {
+    return (wg_gemm_ln_supported(M, N, K, lda, ldw, ldc) && N % 256 == 0 && N <= 1280 &&
+            ((long)(N / 256) * (long)((M + 255) / 256 * 256) * 8 < (1L << 31))) ? 1 : 0;
+}
+extern "C" int wg_gemm_bias_act_stats_bf16(const void* A, long lda, const void* W, long ldw, const void* bias, const void* residual, long ldr,
+                                           int res_row_mod, void* C, long ldc, int M, int N, int K, int act, float* row_partials, long mpad,
+                                           void* stream) {
+    WG_REQUIRE(row_partials && ((uintptr_t)row_partials & 15) == 0, "gemm_stats: row_partials must be a 16-byte aligned buffer");
+    WG_REQUIRE(mpad % 256 == 0 && mpad >= M, "gemm_stats: mpad = %ld must be M = %d rounded up to a multiple of 256", mpad, M);
+    WG_REQUIRE(wg_gemm_row_partials_supported(M, N, K, lda, ldw, ldc) && ((uintptr_t)C & 15) == 0 && (!bias || ((uintptr_t)bias & 15) == 0) &&
+                   (!residual || (ldr % 8 == 0 && ((uintptr_t)residual & 15) == 0)),
+               "gemm_stats: shape M=%d N=%d K=%d does not run on the persistent 256x256 kernel with whole column tiles", M, N, K);
+    GemmArgs g = wg_gemm_args(A, lda, W, ldw, C, ldc, M, N, K, act);
+    g.bias = (const bf16*)bias; g.R = (const bf16*)residual; g.ldr = ldr; g.res_mod = res_row_mod;
+    g.stats_part = row_partials; g.stats_mpad = mpad;
+    return wg_gemm_launch(g, 16, (hipStream_t)stream);
+}
+// The consuming side: wg_gemm_ln_bias_act_bf16 with the statistics given as the producer's partial sums (n_partials planes of mpad
+// rows; n_partials * 256 = K = the LayerNorm width, n_partials <= 5).  eps: the LayerNorm's.
+extern "C" int wg_gemm_lnp_bias_act_bf16(const void* A, long lda, const void* Wg, long ldw, const float* bias_f32, const float* colsum,
+                                         const float* row_partials, int n_partials, long mpad, float eps, void* C, long ldc, int M, int N, int K,
+                                         int act, void* stream) {
+    WG_REQUIRE(bias_f32 && colsum && row_partials, "gemm_lnp: null operand");
+    WG_REQUIRE((((uintptr_t)bias_f32 | (uintptr_t)colsum | (uintptr_t)row_partials) & 15) == 0, "gemm_lnp: misaligned operand");
+    WG_REQUIRE(n_partials >= 1 && n_partials <= 5 && n_partials * 256 == K, "gemm_lnp: %d partial planes do not cover K = %d", n_partials, K);
+    WG_REQUIRE(mpad % 256 == 0 && mpad >= M, "gemm_lnp: mpad = %ld must be M = %d rounded up to a multiple of 256", mpad, M);
+    WG_REQUIRE(wg_gemm_ln_supported(M, N, K, lda, ldw, ldc) && ((uintptr_t)C & 15) == 0, "gemm_lnp: shape M=%d N=%d K=%d does not run on the persistent 256x256 kernel", M, N, K);
+    GemmArgs g = wg_gemm_args(A, lda, Wg, ldw, C, ldc, M, N, K, act);
+    g.ln_s = colsum; g.ln_b = bias_f32; g.ln_part = row_partials; g.ln_np = n_partials; g.ln_mpad = mpad; g.ln_eps = eps;
+    return wg_gemm_launch(g, 16, (hipStream_t)stream);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // fp8 (OCP e4m3) GEMM with per-row / per-output-channel scales (BASELINE config C5):
@@ -2047,28 +2060,13 @@ extern "C" int wg_gemm_mxfp8(const void* Aq, long lda, const void* a_mx, long a_
     WG_REQUIRE(!stats_part || (N % 256 == 0 && stats_mpad % 256 == 0 && stats_mpad >= M && !ln_colsum), "gemm_mxfp8: row partials need N %% 256 == 0 and a pitch covering M (not together with a folded LayerNorm)");
     WG_REQUIRE(!Cq || (c_mx && N % 32 == 0 && ldcq >= N && ldcq % 8 == 0 && c_pitch >= mpad && c_pitch % 4 == 0 && ((uintptr_t)Cq & 7) == 0 && ((uintptr_t)c_mx & 3) == 0),
                "gemm_mxfp8: the fp8 copy needs N %% 32 == 0, ldcq %% 8 == 0 and a scale pitch covering %ld rows", mpad);
-    GemmArgs g;
-    g.A = (const bf16*)Aq; g.lda = lda / 2; g.W = (const bf16*)Wq; g.ldw = ldw / 2;      // the kernel counts 2-byte elements: byte PAIRS
+    GemmArgs g = wg_gemm_args(Aq, lda / 2, Wq, ldw / 2, C, C ? ldc : 0, M, N, K / 2, act);   // the kernel counts 2-byte elements: byte PAIRS
     g.bias = (const bf16*)bias; g.R = (const bf16*)residual; g.ldr = ldr; g.res_mod = res_row_mod;
-    g.C = C; g.ldc = C ? ldc : 0; g.M = M; g.N = N; g.K = K / 2; g.act = act; g.out_f32 = 0;
-    g.tiles_m = g.tiles_n = 0;
-    g.col_block = 0;
-    g.ln_stats = nullptr; g.ln_s = ln_colsum; g.ln_b = ln_bias;
-    g.ln_part = ln_colsum ? ln_part : nullptr; g.ln_np = ln_np; g.ln_mpad = ln_mpad; g.ln_eps = ln_eps;
+    g.ln_s = ln_colsum; g.ln_b = ln_bias; g.ln_part = ln_colsum ? ln_part : nullptr; g.ln_np = ln_np; g.ln_mpad = ln_mpad; g.ln_eps = ln_eps;
     g.stats_part = stats_part; g.stats_mpad = stats_mpad;
-    g.scale_a = g.scale_w = nullptr;
     g.mx_a = (const unsigned char*)a_mx; g.mx_a_pitch = a_pitch; g.mx_w = (const unsigned char*)w_mx; g.mx_w_pitch = w_pitch;
     g.Cq = Cq; g.ldcq = ldcq; g.mx_c = (unsigned char*)(Cq ? c_mx : nullptr); g.mx_c_pitch = c_pitch;
-    g.sk_gamma = g.sk_beta = nullptr; g.sk_eps = 0.f; g.sk_tiled = 0;
-    const long cb = C ? ((long)(M - 1) * ldc + N) * 2 : 0;
-    const long rrows = res_row_mod > 0 ? (res_row_mod < M ? res_row_mod : M) : M;
-    const long rb = residual ? ((rrows - 1) * ldr + N) * 2 : 0;
-    const long qb = Cq ? (long)(M - 1) * ldcq + N : 0, sb = Cq ? (long)(N / 32) * c_pitch : 0;
-    WG_REQUIRE(cb < (1L << 31) && rb < (1L << 31) && qb < (1L << 31) && sb < (1L << 31), "gemm_mxfp8: output larger than 2 GiB");
-    g.c_bytes = (unsigned)cb;
-    g.r_bytes = (unsigned)rb;
-    g.cq_bytes = (unsigned)qb;
-    g.mx_c_bytes = (unsigned)sb;
+    WG_REQUIRE(wg_gemm_extents(g), "gemm_mxfp8: output larger than 2 GiB");
     return launch_pp_persist(g, (hipStream_t)stream);
 }
 
@@ -2088,22 +2086,10 @@ extern "C" int wg_gemm_fp8_bias_act(const void* Aq, long lda, const float* scale
     WG_REQUIRE((((uintptr_t)Aq | (uintptr_t)Wq | (uintptr_t)C) & 15) == 0 && (!bias || ((uintptr_t)bias & 7) == 0) &&
                    (!residual || ((uintptr_t)residual & 15) == 0), "gemm_fp8: misaligned operand");
     WG_REQUIRE((long)M * lda < (1L << 31) && (long)N * ldw < (1L << 31), "gemm_fp8: operand larger than 2 GiB");
-    GemmArgs g;
     // the kernel's address arithmetic counts 2-byte elements: hand it byte PAIRS (a 128-byte slab = "64 elements")
-    g.A = (const bf16*)Aq; g.lda = lda / 2; g.W = (const bf16*)Wq; g.ldw = ldw / 2;
+    GemmArgs g = wg_gemm_args(Aq, lda / 2, Wq, ldw / 2, C, ldc, M, N, K / 2, act);
     g.bias = (const bf16*)bias; g.R = (const bf16*)residual; g.ldr = ldr; g.res_mod = res_row_mod;
-    g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K / 2; g.act = act; g.out_f32 = 0;
-    g.tiles_m = g.tiles_n = 0;
-    g.col_block = 0;
-    g.ln_stats = nullptr; g.ln_s = nullptr; g.ln_b = nullptr;
-    g.ln_part = nullptr; g.ln_np = 0; g.ln_mpad = 0; g.ln_eps = 0.f; g.stats_part = nullptr; g.stats_mpad = 0;
     g.scale_a = scale_a; g.scale_w = scale_w;
-    g.sk_gamma = g.sk_beta = nullptr; g.sk_eps = 0.f; g.sk_tiled = 0;
-    const long cb = ((long)(M - 1) * ldc + N) * 2;
-    const long rrows = res_row_mod > 0 ? (res_row_mod < M ? res_row_mod : M) : M;
-    const long rb = residual ? ((rrows - 1) * ldr + N) * 2 : 0;
-    WG_REQUIRE(cb < (1L << 31) && rb < (1L << 31), "gemm_fp8: output larger than 2 GiB");
-    g.c_bytes = (unsigned)cb;
-    g.r_bytes = (unsigned)rb;
+    WG_REQUIRE(wg_gemm_extents(g), "gemm_fp8: output larger than 2 GiB");
     return launch_tile_impl<256, 256, 64, 2, 2, 4, true, 2, true>(g, (hipStream_t)stream);
 }

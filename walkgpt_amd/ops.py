@@ -60,12 +60,22 @@ def time_gemms():
 
 
 def _timed(kid, M, N, K):
+    """Opens the bracket around one GEMM launch: inside time_gemms() records its start event and returns the pair, else None.
+    _checked(ev, rc, what) closes it after the launch.  (Two plain calls, no closure: this is on every launch's path.)"""
     rec = getattr(_tls, "gemm_records", None)
     if rec is None:
         return None
     ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
     rec.append((kid, M, N, K, ev[0], ev[1]))
+    ev[0].record()
     return ev
+
+
+def _checked(ev, rc, what):
+    if ev is not None:
+        ev[1].record()
+    if rc != 0:
+        _lib.check(rc, what)
 
 
 def gemm_tile_for(M, N, K, lda, ldw, ldc, ldr, tail_tiles=False):
@@ -87,6 +97,22 @@ def _forget_sidecars(t):
                 delattr(t, a)
 
 
+def _out(out, x, N, dtype=_BF16):
+    """The result tensor [..., N] of a GEMM on rows x: the caller's `out` (minus what earlier producers attached to it), else a new one."""
+    _forget_sidecars(out)
+    if out is None:
+        out = torch.empty(x.shape[:-1] + (N,), device=x.device, dtype=dtype)
+    return out
+
+
+def _residual_ld(residual):
+    """Leading dimension of a bf16 residual operand (0: none)."""
+    if residual is None:
+        return 0
+    assert residual.dtype == _BF16
+    return _rows(residual)[2]
+
+
 def linear(x, weight, bias=None, act=ACT_NONE, residual=None, res_row_mod=0, out=None, out_f32=False, tile=0, tail_tiles=False,
            row_partials=False):
     """y = act(x @ weight.T + bias) (+ residual).  x [..., K] bf16, weight [N, K] bf16.
@@ -98,16 +124,11 @@ def linear(x, weight, bias=None, act=ACT_NONE, residual=None, res_row_mod=0, out
     M, K, lda = _rows(x)
     N, K2 = weight.shape
     assert K2 == K and weight.stride(1) == 1
-    _forget_sidecars(out)
-    if out is None:
-        out = torch.empty(x.shape[:-1] + (N,), device=x.device, dtype=torch.float32 if out_f32 else _BF16)
+    out = _out(out, x, N, torch.float32 if out_f32 else _BF16)
     Mo, No, ldc = _rows(out)
     assert Mo == M and No == N
-    ldr = 0
-    if residual is not None:
-        assert residual.dtype == _BF16
-        _, Nr, ldr = _rows(residual)
-        assert Nr == N
+    ldr = _residual_ld(residual)
+    assert residual is None or residual.shape[-1] == N
     if bias is not None:
         assert bias.dtype == _BF16 and bias.numel() == N
     if (row_partials and not out_f32 and tile == 0 and not tail_tiles
@@ -116,26 +137,18 @@ def linear(x, weight, bias=None, act=ACT_NONE, residual=None, res_row_mod=0, out
         mpad = (M + 255) // 256 * 256
         part = torch.empty(N // 256, mpad, 2, device=x.device, dtype=torch.float32)
         ev = _timed(18, M, N, K)  # 18: the statistics-producing instance of kernel 16
-        if ev is not None:
-            ev[0].record()
         rc = _lib.lib().wg_gemm_bias_act_stats_bf16(x.data_ptr(), lda, weight.data_ptr(), weight.stride(0), _ptr(bias), _ptr(residual), ldr,
                                                     res_row_mod, out.data_ptr(), ldc, M, N, K, act, part.data_ptr(), mpad, _stream())
-        if ev is not None:
-            ev[1].record()
-        _lib.check(rc, "wg_gemm_bias_act_stats_bf16")
+        _checked(ev, rc, "wg_gemm_bias_act_stats_bf16")
         out._wg_row_partials = (part, mpad, out._version, M, N)
         return out
     if tile == 0:
         tile = gemm_tile_for(M, N, K, lda, weight.stride(0), ldc, ldr, tail_tiles)
     ev = _timed(tile, M, N, K)
-    if ev is not None:
-        ev[0].record()
     rc = _lib.lib().wg_gemm_bias_act_bf16(x.data_ptr(), lda, weight.data_ptr(), weight.stride(0), _ptr(bias),
                                           _ptr(residual), ldr, res_row_mod, out.data_ptr(), ldc, M, N, K, act,
                                           1 if out.dtype == torch.float32 else 0, tile, _stream())
-    if ev is not None:
-        ev[1].record()
-    _lib.check(rc, "wg_gemm_bias_act_bf16")
+    _checked(ev, rc, "wg_gemm_bias_act_bf16")
     return out
 
 
@@ -191,23 +204,15 @@ def ln_linear(x, fold, eps, act=ACT_NONE, tail_tiles=False):
         # the GEMM that wrote x left its rows' partial sums (linear(..., row_partials=True)): no statistics pass
         part, mpad = rp[0], rp[1]
         ev = _timed(17, M, N, K)
-        if ev is not None:
-            ev[0].record()
         rc = L.wg_gemm_lnp_bias_act_bf16(x.data_ptr(), lda, fold["wg"].data_ptr(), K, fold["bias_f32"].data_ptr(), fold["colsum"].data_ptr(),
                                          part.data_ptr(), part.shape[0], mpad, float(eps), out.data_ptr(), N, M, N, K, act, _stream())
-        if ev is not None:
-            ev[1].record()
-        _lib.check(rc, "wg_gemm_lnp_bias_act_bf16")
+        _checked(ev, rc, "wg_gemm_lnp_bias_act_bf16")
         return out
     st = row_stats(x, eps)
     ev = _timed(17, M, N, K)  # 17: the LayerNorm-folded instance of kernel 16
-    if ev is not None:
-        ev[0].record()
     rc = L.wg_gemm_ln_bias_act_bf16(x.data_ptr(), lda, fold["wg"].data_ptr(), K, fold["bias_f32"].data_ptr(),
                                     fold["colsum"].data_ptr(), st.data_ptr(), out.data_ptr(), N, M, N, K, act, _stream())
-    if ev is not None:
-        ev[1].record()
-    _lib.check(rc, "wg_gemm_ln_bias_act_bf16")
+    _checked(ev, rc, "wg_gemm_ln_bias_act_bf16")
     return out
 
 
@@ -227,15 +232,11 @@ def layernorm_linear(x, gamma, beta, eps, weight, bias=None, act=ACT_NONE, out_f
     assert weight_tiled is None or _tiled_ok(weight_tiled, N, K)
     out = torch.empty(x.shape[:-1] + (N,), device=x.device, dtype=torch.float32 if out_f32 else _BF16)
     ev = _timed(5, M, N, K)
-    if ev is not None:
-        ev[0].record()
     w = weight if weight_tiled is None else weight_tiled
     rc = L.wg_gemm_skinny_ln_bias_act_bf16(x.data_ptr(), lda, _ptr(gamma), _ptr(beta), float(eps), w.data_ptr(), weight.stride(0),
                                            0 if weight_tiled is None else 1, _ptr(bias), out.data_ptr(), N, M, N, K, act,
                                            1 if out_f32 else 0, _stream())
-    if ev is not None:
-        ev[1].record()
-    _lib.check(rc, "wg_gemm_skinny_ln_bias_act_bf16")
+    _checked(ev, rc, "wg_gemm_skinny_ln_bias_act_bf16")
     return out
 
 
@@ -576,10 +577,7 @@ def linear_mxfp8(x, w, bias=None, act=ACT_NONE, residual=None, res_row_mod=0, ou
     if out is None and bf16_out:
         out = torch.empty(xq.shape[:-1] + (N,), device=dev, dtype=_BF16)
     ldc = _rows(out)[2] if out is not None else 0
-    ldr = 0
-    if residual is not None:
-        assert residual.dtype == _BF16
-        _, _, ldr = _rows(residual)
+    ldr = _residual_ld(residual)
     cq = cmx = part = None
     if mx_out:
         cq = torch.empty(xq.shape[:-1] + (N,), device=dev, dtype=torch.uint8)
@@ -588,8 +586,6 @@ def linear_mxfp8(x, w, bias=None, act=ACT_NONE, residual=None, res_row_mod=0, ou
         assert N % 256 == 0 and ln is None
         part = torch.empty(N // 256, mx_pitch(M), 2, device=dev, dtype=torch.float32)
     ev = _timed(22 if ln is not None else (23 if row_partials else 21), M, N, K)   # (ids: bench.py KERNEL_NAMES)
-    if ev is not None:
-        ev[0].record()
     rc = _lib.lib().wg_gemm_mxfp8(xq.data_ptr(), K, x_mx.data_ptr(), x_mx.shape[1], wq.data_ptr(), K, w_mx.data_ptr(), w_mx.shape[1],
                                   None if ln is not None else _ptr(bias),
                                   w["colsum"].data_ptr() if ln is not None else None, w["bias_f32"].data_ptr() if ln is not None else None,
@@ -597,9 +593,7 @@ def linear_mxfp8(x, w, bias=None, act=ACT_NONE, residual=None, res_row_mod=0, ou
                                   ln[1] if ln is not None else 0, float(ln_eps) if ln is not None else 0.0,
                                   _ptr(residual), ldr, res_row_mod, _ptr(out), ldc, _ptr(cq), N, _ptr(cmx), cmx.shape[1] if mx_out else 0,
                                   _ptr(part), part.shape[1] if row_partials else 0, M, N, K, act, _stream())
-    if ev is not None:
-        ev[1].record()
-    _lib.check(rc, "wg_gemm_mxfp8")
+    _checked(ev, rc, "wg_gemm_mxfp8")
     if not bf16_out:
         return cq, cmx
     if mx_out:
@@ -618,22 +612,13 @@ def linear_fp8(xq, x_scale, wq, w_scale, bias=None, act=ACT_NONE, residual=None,
     M = xq.numel() // K
     N = wq.shape[0]
     assert wq.shape[1] == K and x_scale.numel() == M and w_scale.numel() == N
-    _forget_sidecars(out)
-    if out is None:
-        out = torch.empty(xq.shape[:-1] + (N,), device=xq.device, dtype=_BF16)
+    out = _out(out, xq, N)
     _, _, ldc = _rows(out)
-    ldr = 0
-    if residual is not None:
-        assert residual.dtype == _BF16
-        _, _, ldr = _rows(residual)
+    ldr = _residual_ld(residual)
     ev = _timed(20, M, N, K)
-    if ev is not None:
-        ev[0].record()
     rc = _lib.lib().wg_gemm_fp8_bias_act(xq.data_ptr(), K, x_scale.data_ptr(), wq.data_ptr(), K, w_scale.data_ptr(), _ptr(bias),
                                          _ptr(residual), ldr, res_row_mod, out.data_ptr(), ldc, M, N, K, act, _stream())
-    if ev is not None:
-        ev[1].record()
-    _lib.check(rc, "wg_gemm_fp8_bias_act")
+    _checked(ev, rc, "wg_gemm_fp8_bias_act")
     return out
 
 
