@@ -305,6 +305,30 @@ def test_hand_placed_streams_have_no_unpadded_mfma_operand(source):
     assert r.returncode == 0, r.stdout + r.stderr
 
 
+_ATTN_KERNELS = (   # every kernel attn.hip and attn_window_unit.hip instantiate: <head_dim, S, waves, key bias> / <head_dim, S, waves>
+    ["_Z14wg_attn_kernelILi%dELi%dELi%dELb%dEEv8AttnArgs" % k for k in
+     [(hd, 0, nw, kb) for hd, nws in ((16, (1,)), (32, (1, 4, 8)), (64, (1, 3, 4, 8)), (128, (1, 4, 8))) for nw in nws for kb in (0, 1)]
+     + [(64, 64, 8, 0), (80, 64, 8, 0)]]
+    + ["_Z21wg_attn_window_kernelILi%dELi%dELi%dEEv8AttnArgsi" % k for k in [(64, 14, 4), (64, 32, 8), (32, 14, 7), (32, 28, 5), (80, 14, 7)]]
+    + ["_Z26wg_attn_window_unit_kernelILi64ELi14ELi7EEv8AttnArgsi"])
+
+
+def test_attention_kernels_are_the_recorded_set_and_do_not_spill():
+    """tools/isa_fingerprint.py on the two attention sources: exactly the 29 + 1 kernels the routers reach are compiled (plain and global
+    wg_attn_kernel, the five windows, the unit kernel -- a template argument nobody launches would show up here), and none of them has a
+    private segment, i.e. no register spills to scratch (several sit at 250+ VGPRs)."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_fingerprint.py")]
+                       + [os.path.join(ROOT, "walkgpt_amd", "csrc", f) for f in ("attn.hip", "attn_window_unit.hip")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    rows = [ln.split() for ln in r.stdout.splitlines()]
+    assert len(_ATTN_KERNELS) == 30 and sorted(row[0] for row in rows) == sorted(_ATTN_KERNELS)
+    for row in rows:
+        assert re.fullmatch(r"[0-9a-f]{16}", row[1]) and [f.split("=")[0] for f in row[2:]] == ["vgpr", "agpr", "sgpr", "lds", "private"], row
+        assert row[-1] == "private=0", "%s spills: %s" % (row[0], " ".join(row[2:]))
+
+
 def test_environment_and_macros_choose_no_code_path():
     """What the library and the host path compute depends on their arguments alone: no environment variable picks a kernel, tile order or
     fusion, and the only compile-time switches left are the diagnostic stamp builds.  The build may read HIPCC / WG_EXTRA_HIPCC_FLAGS and

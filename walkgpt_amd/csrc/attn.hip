@@ -1,12 +1,14 @@
 // Fused multi-head attention for gfx950 (flash style: the score matrix never leaves registers).
 //
-// One kernel template, three users on the hot path:
-//   S == 0  "plain"  : CLIP ViT-L/14 self-attention, 1025 keys + additive key-padding mask
-//                      (custom_clip.py:27-38,50-104; HF CLIPAttention), MSQP cross-attention.
-//   S == 14 "window" : SAM 14x14 windowed attention incl. decomposed rel-pos and the 64->70 zero padding whose
-//                      pad tokens carry q=k=v=qkv-bias and take part in the softmax as keys
-//                      (image_encoder.py:177-193, 235-260, 263-318, 321-392).
-//   S == grid side   : SAM global attention (4096 keys at S=64) with decomposed rel-pos.
+// Which kernel serves which user:
+//   plain (wg_mha_bf16)            : wg_attn_kernel<HD, 0, NW, KB> -- CLIP ViT-L/14 self-attention, 1025 keys + additive key-padding mask
+//                                    (KB), MSQP cross-attention; head_dim 16 / 32 / 64 / 128.
+//   global (window == grid == 64)  : wg_attn_kernel<HD, 64, 8, false> -- SAM global attention, 4096 keys, decomposed rel-pos.
+//   windows (window <= 32)         : wg_attn_window_kernel<HD, S, NW> (below) -- SAM 14 x 14 windows incl. decomposed rel-pos and the
+//                                    64 -> 70 zero padding whose pad tokens carry q = k = v = qkv-bias and take part in the softmax as keys.
+//   head_dim 64, windows of 14     : wg_attn_window_unit_kernel<64, 14, 7> (attn_window_unit.hip), a whole (window, head) of K / V ahead.
+//   head_dim 64, global and, where wg_attn_pipe_takes() says so, plain: wg_attn_pipe_kernel (attn_pipe.hip), the hand-placed loop.
+// The tile geometry and each kernel's LDS layout are stated once, in attn_common.h (AttnGeom, *Lds), for kernels and launchers alike.
 // window_partition / window_unpartition are pure address arithmetic here (no copies): keys and queries are fetched
 // from / written to their natural [B*H*W, 3D] / [B*H*W, D] rows.
 //
@@ -17,10 +19,10 @@
 //                    exchange with lane^32).
 //   O^T += V^T . P^T (P^T is the S^T accumulator converted to bf16 in place: "accumulator as the next MFMA's
 //                    B operand", k order permuted; the matching V^T fragment is read with ds_read_b64_tr_b16.)
-//   rel-pos: T^T = Rel . Q^T by MFMA (table rows straight from global as the A operand), scattered into a
-//            per-wave key-space table relh[q][kh], relw[q][kw] in LDS (pre-multiplied by log2 e); the main loop adds
-//            relh[q][k / S] + relw[q][k % S].  For S == 64 a key tile is exactly one grid row: relw lives in 32
-//            registers and relh costs one LDS read per tile.
+//   rel-pos: T^T = Rel . Q^T by MFMA, scattered into a per-wave key-space table relh[q][kh], relw[q][kw] in LDS (pre-multiplied
+//            by log2 e).  The width term then moves to registers and enters the scores as the C operand of a tile's first S^T MFMAs;
+//            the height term is read from LDS per tile: one value per lane where a tile is one grid row (S == 64), one per padded
+//            window row of the tile otherwise.
 // LDS swizzles (source-side, undone on the read): K rows for ds_read_b128, V rows for the transposed read.
 #include "wg_common.h"
 #include <type_traits>
@@ -47,34 +49,20 @@ extern "C" int wg_debug_attn_stamps(unsigned* buf) {
 
 template <int HD, int S, int NW, bool KB>
 __global__ __launch_bounds__(NW * 64, 2) void wg_attn_kernel(AttnArgs a) {
-    constexpr int HDP = (HD == 80) ? 96 : (HD == 16 ? 32 : HD);  // head dim padded to a multiple of 32 inside LDS
-    // head_dim 80: rows padded once more to 13 chunks = 52 dwords, a pitch that sends 16 consecutive rows to 16 different bank
-    // quads (the K fragment reads of 192-byte rows were 4-way conflicted: rows r and r + 4 shared their banks); the 13th chunk of
-    // a row is never read
-    constexpr int ROWB = (HD == 80) ? 208 : HDP * 2;   // bytes per K row
-    // V rows of head_dim 80 keep the natural 192-byte pitch (12 chunks): four consecutive rows x 16 dwords then fall on disjoint bank
-    // ranges for the transposed reads (pitch 48 dwords: 0, 48, 32, 16 mod 64), which the 208-byte pitch of the K rows (0, 52, 40, 28: rows
-    // r and r + 1 overlap by four banks, a 2-way conflict) does not give; K keeps 208 for its ds_read_b128 pattern
-    constexpr int ROWBV = (HD == 80) ? 192 : ROWB;     // bytes per V row
-    constexpr int TILE = 64 * ROWB;        // bytes per K tile
-    constexpr int TILEV = 64 * ROWBV;      // bytes per V tile
-    constexpr int TILE2 = TILE + TILEV;    // one buffer = K tile | V tile
-    constexpr int KSTEPS = HD / 16;        // QK^T runs over the real head dim only
-    constexpr int DB = HDP / 32;           // PV d-blocks; columns >= HD hold don't-care data and are never stored
+    static_assert(S == 0 || S == 64, "plain attention or a 64 x 64 global grid (windows: wg_attn_window_kernel)");
+    static_assert(!(S > 0 && KB), "the key bias belongs to plain mode");
+    using G = AttnGeom<HD, S>;   // (attn_common.h: what each constant means)
+    constexpr int HDP = G::HDP, ROWB = G::ROWB, ROWBV = G::ROWBV, TILE = G::TILE, TILEV = G::TILEV, TILE2 = G::TILE2, KSTEPS = G::KSTEPS, DB = G::DB;
     constexpr bool GRID = (S > 0);
-    constexpr int SS = GRID ? S * S : 0;
-    // Grid mode key order: window rows padded to RP slots (16 / 32 / 64), RPT rows per 64-key tile.  A key slot's
-    // column (kw) then depends only on the accumulator register, its row (kh) only on (tile, register): the width term
-    // of the rel-pos bias is RP/2 registers per lane, the height term RPT LDS reads per tile, and padding slots are
-    // masked by -inf entries in those two tables instead of per-element tests.
-    constexpr int RP = S <= 16 ? 16 : (S <= 32 ? 32 : 64);
-    constexpr int RPT = 64 / RP;
-    constexpr int NTG = GRID ? (S + RPT - 1) / RPT : 0;   // key tiles per window
-    constexpr int SP = GRID ? NTG * RPT + 1 : 1;          // relh table row (fp32 words, odd => conflict-free)
-    constexpr int NRW = GRID ? RP / 2 : 1;                // width-bias registers per lane
+    constexpr int SS = S * S;
+    // Grid mode: a 64-key tile is exactly one grid row (RP == 64, RPT == 1): the width term of the rel-pos bias is 32 registers per lane,
+    // the height term one LDS read per tile.
+    constexpr int RP = G::RP, NTG = G::NTG, SP = G::SP;
+    static_assert(!GRID || G::RPT == 1);
+    constexpr AttnLds L = wg_attn_lds<HD, S>(NW, 0);
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* kv = smem;                                  // [2 buffers][K tile | V tile]
-    float* tab = (float*)(smem + 2 * TILE2);          // grid: per-wave rel table; plain: key bias row
+    char* kv = smem + L.kv;                           // [2 buffers][K tile | V tile]
+    float* tab = (float*)(smem + L.tab);              // grid: per-wave rel table; plain: key bias row
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -108,7 +96,7 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_kernel(AttnArgs a) {
         b = bw;
     }
     const int Lq = GRID ? SS : a.Lq;
-    const int Lk = GRID ? NTG * 64 : a.Lk;   // grid mode: every slot of every tile is either a key or masked by the tables
+    const int Lk = GRID ? NTG * 64 : a.Lk;
     const int hcol = head * HD;
 
     // ---- this lane's query ---------------------------------------------------------------------------------------
@@ -128,26 +116,7 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_kernel(AttnArgs a) {
         qrow = (long)b * a.q_bs + ql;
     }
     bf16x8 qf[KSTEPS];
-    {
-        const bf16* qp = a.Q + qrow * a.ldq + hcol + 8 * hi;
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) qf[s] = *(const bf16x8*)(qp + 16 * s);
-    }
-
-    // Window-sized tables (2S-1 <= 32 rows): the rel-pos rows of BOTH passes below are requested here, together with the query,
-    // so that the prologue waits for global memory once instead of three times (query, width rows, height rows) -- with four key
-    // tiles per window the prologue is as long as the loop.
-    constexpr int NJB = GRID ? (2 * S - 1 + 31) / 32 : 1;
-    constexpr bool REL_EARLY = GRID && NJB == 1;
-    bf16x8 rel_early[REL_EARLY ? 2 : 1][KSTEPS];
-    if constexpr (REL_EARLY) {
-        const int j = ql_lane < 2 * S - 1 ? ql_lane : 2 * S - 2;
-#pragma unroll
-        for (int which = 0; which < 2; ++which)
-#pragma unroll
-            for (int s = 0; s < KSTEPS; ++s)
-                rel_early[which][s] = *(const bf16x8*)((which == 0 ? a.rel_w : a.rel_h) + (long)j * HD + 16 * s + 8 * hi);
-    }
+    wg_attn_load_q<KSTEPS>(a, qrow, hcol, hi, qf);
 
     // ---- K/V staging (LDS-DMA, swizzle on the source address) -----------------------------------------------
     // Piece i of this wave (1 KiB = 64 lanes x 16 bytes) covers fixed key slots of every tile, so its source is a running
@@ -155,13 +124,14 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_kernel(AttnArgs a) {
     // arithmetic -- window -> image coordinates, clamps, 64-bit row offsets -- was ~25 VALU instructions per piece per tile,
     // as much as the exponentials).  Slots that do not exist in a tile (keys beyond Lk; window rows beyond the window or the
     // image) read the substitute row instead: the last key (plain) or the qkv-bias row that stands for zero padding (grid);
-    // slots beyond the window width do so in every tile and keep a stride of 0.  Their scores are masked by the bias tables.
+    // columns beyond the image do so in every tile and keep a stride of 0.  Their scores are masked by the bias tables.
     constexpr int NINSTK = TILE / 1024, NINSTV = TILEV / 1024;   // wave-instructions per K / V tile
     constexpr int NPW = (NINSTK + NW - 1) / NW;                    // ... per wave (NINSTV <= NINSTK)
     const bf16* altK = GRID ? a.padK + hcol : a.K + ((long)b * a.k_bs + (a.Lk - 1)) * a.ldk + hcol;
     const bf16* altV = GRID ? a.padV + hcol : a.V + ((long)b * a.k_bs + (a.Lk - 1)) * a.ldv + hcol;
     const int klim0 = GRID ? (S < a.Hg - wy * S ? S : a.Hg - wy * S) : a.Lk;   // rows (grid) / keys (plain) that exist
     constexpr bool RUNP = NPW <= 3;   // (one-wave workgroups issue every piece themselves: they keep the general form)
+    static_assert(RUNP || !GRID, "the general form is written for plain mode only");
     constexpr int NRP = RUNP ? NPW : 1;
     const bf16* runp[2][NRP];
     unsigned coff[2][NRP];
@@ -180,9 +150,8 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_kernel(AttnArgs a) {
                 if (HDP != HD && c * 8 >= HD) c = HD / 8 - 1;   // pad columns: any readable bytes will do
                 coff[o][i] = c * 8;
                 long r;
-                if (GRID) {
-                    int kw = row % RP;
-                    kw = kw < S ? kw : S - 1;
+                if (GRID) {           // (slot kw of every tile is grid column kw)
+                    const int kw = row % RP;
                     kslot[o][i] = row / RP;
                     padx[o][i] = wx * S + kw >= a.Hg;
                     r = (long)b * a.Hg * a.Hg + (long)(wy * S + kslot[o][i]) * a.Hg + wx * S + kw;
@@ -196,12 +165,12 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_kernel(AttnArgs a) {
             }
         }
     }
-    const unsigned strideK = (unsigned)((GRID ? (long)RPT * a.Hg : 64L) * a.ldk);
-    const unsigned strideV = (unsigned)((GRID ? (long)RPT * a.Hg : 64L) * a.ldv);
+    const unsigned strideK = (unsigned)((GRID ? (long)a.Hg : 64L) * a.ldk);   // one grid row / 64 keys per tile
+    const unsigned strideV = (unsigned)((GRID ? (long)a.Hg : 64L) * a.ldv);
     // tile t of K (or V) -> buffer `buf`; per operand the tiles must be staged in order 0, 1, 2, ... (running pointers)
     auto stage = [&](int t, int buf, bool isV) __attribute__((always_inline)) {
         char* dst = kv + buf * TILE2 + (isV ? TILE : 0);
-        const int lim = klim0 - t * (GRID ? RPT : 64);
+        const int lim = klim0 - t * (GRID ? 1 : 64);
         const int o = isV ? 1 : 0;
         const int cpr = (isV ? ROWBV : ROWB) / 16, ninst = isV ? NINSTV : NINSTK;
         if constexpr (RUNP) {
@@ -221,15 +190,7 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_kernel(AttnArgs a) {
                 int c = cs ^ (isV ? swzV<HD>(row) : swzK<HD>(row));
                 if (HDP != HD && c * 8 >= HD) c = HD / 8 - 1;
                 const bf16* src = (isV ? altV : altK) + c * 8;
-                if (GRID) {
-                    int kw = row % RP;
-                    kw = kw < S ? kw : S - 1;
-                    const int kh = t * RPT + row / RP;
-                    if (row / RP < lim && wx * S + kw < a.Hg) {
-                        const long r = (long)b * a.Hg * a.Hg + (long)(wy * S + kh) * a.Hg + wx * S + kw;
-                        src = (isV ? a.V + r * a.ldv : a.K + r * a.ldk) + hcol + c * 8;
-                    }
-                } else if (row < lim) {
+                if (row < lim) {
                     const long r = (long)b * a.k_bs + t * 64 + row;
                     src = (isV ? a.V + r * a.ldv : a.K + r * a.ldk) + hcol + c * 8;
                 }
@@ -246,11 +207,11 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_kernel(AttnArgs a) {
     stage(0, 0, true);
 
     // ---- rel-pos tables (grid) / key bias row (plain) -----------------------------------------------------------
-    // Width term of the rel-pos bias, laid out as the S^T accumulator of a key block (element r of block kb belongs to padded-row
-    // column slot (16*kb + r) % NRW) and pre-divided by scale*log2(e): it is the C operand of the first S^T MFMA of every tile,
-    // so the matrix pipe adds it and the scores leave the MFMAs as (q.k + relw / sc2).
-    constexpr int NC = (GRID && RP == 64) ? 2 : 1;
-    f32x16 relw_c[NC];
+    // Width term of the rel-pos bias, laid out as the S^T accumulators of the two key blocks (element r of block kb belongs to grid
+    // column 32 kb + (r & 3) + 8 (r >> 2) + 4 hi) and pre-divided by scale*log2(e): it is the C operand of the first S^T MFMA of every
+    // tile, so the matrix pipe adds it and the scores leave the MFMAs as (q.k + relw / sc2).
+    constexpr int NJB = (2 * S - 1 + 31) / 32;   // 32-row blocks of a rel-pos table
+    f32x16 relw_c[2];
     float* mytab = tab + wave * 32 * SP;
     // T^T = Rel . Q^T for one of the two tables, scattered to key space: mytab[q][kpos]
     auto rel_pass = [&](int which) __attribute__((always_inline)) {
@@ -266,9 +227,7 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_kernel(AttnArgs a) {
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
             for (int s = 0; s < KSTEPS; ++s) {
-                bf16x8 rf;
-                if constexpr (REL_EARLY) rf = rel_early[which][s];
-                else rf = *(const bf16x8*)(rel + (long)j * HD + 16 * s + 8 * hi);
+                const bf16x8 rf = *(const bf16x8*)(rel + (long)j * HD + 16 * s + 8 * hi);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rf, qf[s], acc, 0, 0, 0);
             }
 #pragma unroll
@@ -287,10 +246,9 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_kernel(AttnArgs a) {
         rel_pass(0);
         asm volatile("" ::: "memory");
 #pragma unroll
-        for (int e = 0; e < 16 * NC; ++e) {
-            const int j = e % NRW;
-            const int kw = (j & 3) + 8 * (j >> 2) + 4 * hi;   // this lane's j-th column slot inside a padded row
-            relw_c[e >> 4][e & 15] = (kw < S ? mytab[ql_lane * SP + kw] : NEG_BIG) * inv_sc2;
+        for (int e = 0; e < 32; ++e) {
+            const int kw = (e & 3) + 8 * (e >> 2) + 4 * hi;   // this lane's e-th grid column
+            relw_c[e >> 4][e & 15] = mytab[ql_lane * SP + kw] * inv_sc2;
         }
         asm volatile("" ::: "memory");
         rel_pass(1);
@@ -324,9 +282,9 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_kernel(AttnArgs a) {
     // latency chain in an in-order pipeline (matrix pipe 35 %, VALU 46 % busy, 18 % of the time together), not a throughput
     // problem of either unit.
     constexpr float RESCALE_THR = 6.0f;
-    // RAW: no per-element bias is left to add on the VALU (none at all, or -- grid mode with one key row per tile -- the width term
-    // comes out of the MFMAs and the height term is one value per tile): scores stay unscaled, p = exp2(s*sc2 - off)
-    constexpr bool RAW = (!GRID && !KB) || (GRID && RPT == 1);
+    // RAW: no per-element bias is left to add on the VALU (none at all, or -- grid mode -- the width term comes out of the MFMAs and
+    // the height term is one value per tile): scores stay unscaled, p = exp2(s*sc2 - off)
+    constexpr bool RAW = !KB;
     constexpr int NQK = 2 * KSTEPS;              // S^T MFMAs per tile
     constexpr int NPV = 4 * DB;                  // P.V MFMAs per tile
     f32x16 sa[2];                                // scores of the tile
@@ -347,7 +305,7 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_kernel(AttnArgs a) {
         const int kb = g & 1, s = g >> 1;
         if (s == 0) {
             if constexpr (GRID) {
-                st[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[g], qf[s], relw_c[kb % NC], 0, 0, 0);
+                st[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[g], qf[s], relw_c[kb], 0, 0, 0);
             } else {
                 const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                 st[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[g], qf[s], z, 0, 0, 0);
@@ -357,12 +315,11 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_kernel(AttnArgs a) {
         }
     };
     // bias + running max over score elements [e0, e1) of tile t (flattened index e = 16*kb + r)
-    float rh[GRID ? RPT : 1];
+    float rh = 0.f;   // grid mode: the height term of the tile's one key row
     f32x4 kbv[2][4];
     auto bias_begin = [&](int t) __attribute__((always_inline)) {
         if constexpr (GRID) {
-#pragma unroll
-            for (int i = 0; i < RPT; ++i) rh[i] = relh_tab[t * RPT + i];
+            rh = relh_tab[t];
         } else if constexpr (KB) {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
@@ -375,12 +332,7 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_kernel(AttnArgs a) {
         for (int e = e0; e < e1; ++e) {
             const int kb = e >> 4, r = e & 15;
             float v = st[kb][r];
-            if constexpr (GRID && RPT > 1) {
-                const int sl0 = 32 * kb + (r & 3) + 8 * (r >> 2);        // slot in tile without the lane-half bit
-                v = v * sc2 + rh[sl0 / RP];                                // (the width term is already in v: C operand of the MFMA)
-            } else if constexpr (KB) {
-                v = v * sc2 + kbv[kb][r >> 2][r & 3];
-            }
+            if constexpr (KB) v = v * sc2 + kbv[kb][r >> 2][r & 3];
             if (mask_tail && t * 64 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi >= Lk) v = NEG_BIG;
             if (!RAW || mask_tail) st[kb][r] = v;
             mt = fmaxf(mt, v);
@@ -388,8 +340,7 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_kernel(AttnArgs a) {
     };
     // running max across the lane pair, lazy rescale of O; returns the exponent offset of the tile
     auto bias_end = [&](float mt) __attribute__((always_inline)) -> float {
-        float rowh = 0.f;
-        if constexpr (GRID && RPT == 1) rowh = rh[0];
+        const float rowh = rh;
         if constexpr (RAW) mt *= sc2;
         mt += rowh;
         mt = wg_xor32_max(mt);   // the other half of the keys of this query lives in lane ^ 32
@@ -421,16 +372,10 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_kernel(AttnArgs a) {
             vt_ad[d] = vbase + (4 * hi + rq) * ROWBV + ((chunk ^ swzV<HD>(4 * hi + rq)) << 4) + (col & 7) * 2;
         }
     }
-    // the two transposed reads that feed P.V MFMA g = ks*DB + d (the offset must be an immediate: switch on the unrolled ks)
+    // the two transposed reads that feed P.V MFMA g = ks*DB + d
     auto vt_pair = [&](int g, int buf) __attribute__((always_inline)) {
         const int ks = g / DB, d = g % DB;
-        const unsigned ad = vt_ad[d] + (unsigned)(buf * TILE2);
-        switch (ks) {
-            case 0: vt[0][d][0] = wg_ds_read_tr<0 * 16 * ROWBV>(ad); vt[0][d][1] = wg_ds_read_tr<0 * 16 * ROWBV + 8 * ROWBV>(ad); break;
-            case 1: vt[1][d][0] = wg_ds_read_tr<1 * 16 * ROWBV>(ad); vt[1][d][1] = wg_ds_read_tr<1 * 16 * ROWBV + 8 * ROWBV>(ad); break;
-            case 2: vt[2][d][0] = wg_ds_read_tr<2 * 16 * ROWBV>(ad); vt[2][d][1] = wg_ds_read_tr<2 * 16 * ROWBV + 8 * ROWBV>(ad); break;
-            default: vt[3][d][0] = wg_ds_read_tr<3 * 16 * ROWBV>(ad); vt[3][d][1] = wg_ds_read_tr<3 * 16 * ROWBV + 8 * ROWBV>(ad); break;
-        }
+        wg_attn_vt_pair<ROWBV>(ks, vt_ad[d] + (unsigned)(buf * TILE2), vt[ks][d]);
     };
     // exponentials, row sum and bf16 packing of score elements [e0, e1)
     auto probs = [&](const f32x16* st, float off, int e0, int e1) __attribute__((always_inline)) {
@@ -449,8 +394,6 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_kernel(AttnArgs a) {
         ot[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[ks], ot[d], 0, 0, 0);
     };
 
-    // Windows whose last tile holds keys in its first key block only (S = 14 at four padded rows per tile: rows 12, 13 | 14, 15): the dead
-    // block's S^T MFMAs, exponentials, V^T reads and P.V MFMAs are skipped there -- an eighth of a four-tile window's loop.
 #ifndef WG_ATTN_STAMP   // (the diagnostic build keeps every wave to its closing barrier)
     if (!GRID && (qc * NW + wave) * 32 >= Lq) {
         // a wave without a single query (the last chunk of a ragged query count: CLIP's 1025 = 32 blocks + 1 leaves three such waves in
@@ -467,10 +410,9 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_kernel(AttnArgs a) {
         return;
     }
 #endif
-    constexpr bool HALF_LAST = GRID && RPT > 1 && (S % RPT) != 0 && (S % RPT) * RP <= 32;
-    auto tile = [&](int t, auto half_c) __attribute__((always_inline)) {
-        constexpr bool HALF = decltype(half_c)::value;
-        constexpr int NE = HALF ? 16 : 32;           // score elements per lane that can hold a key
+    // (written out here, not instantiated through a generic lambda: that shifts hipcc's register allocation and one head_dim-128 variant
+    // starts to spill)
+    for (int t = 0; t < nt; ++t) {
         const int buf = t & 1;
         WG_STAMP(0);
         if (t + 1 < nt) {
@@ -479,100 +421,39 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_kernel(AttnArgs a) {
         }
         bias_begin(t);
 #pragma unroll
-        for (int g = 0; g < NQK; ++g)
-            if (!HALF || (g & 1) == 0) qk_read(kv + buf * TILE2, g);
+        for (int g = 0; g < NQK; ++g) qk_read(kv + buf * TILE2, g);
 #pragma unroll
-        for (int g = 0; g < NQK; ++g)
-            if (!HALF || (g & 1) == 0) qk_one(sa, g);
+        for (int g = 0; g < NQK; ++g) qk_one(sa, g);
         // V^T fragments: inline-asm reads (invisible to hipcc's wait insertion), issued as early as the registers allow so that
         // their LDS latency hides under the softmax: right behind the S^T MFMAs, or -- key-bias variants, whose bias row
         // occupies 32 registers until it is applied -- after the running max.  Every LDS read hipcc does know about is retired
         // first: its wait would cover these too.
         constexpr bool EARLY_VT = !KB;
-        if constexpr (GRID) {
-#pragma unroll
-            for (int i = 0; i < RPT; ++i) asm volatile("" : "+v"(rh[i]));
-        }
+        if constexpr (GRID) asm volatile("" : "+v"(rh));
         if constexpr (EARLY_VT) {
 #pragma unroll
-            for (int g = 0; g < NPV; ++g)
-                if (!HALF || g / DB < 2) vt_pair(g, buf);
+            for (int g = 0; g < NPV; ++g) vt_pair(g, buf);
         }
         float mt = NEG_BIG;
-        if (ragged && t + 1 == nt) bias_max(sa, t, 0, NE, mt, true);
-        else bias_max(sa, t, 0, NE, mt, false);
+        if (ragged && t + 1 == nt) bias_max(sa, t, 0, 32, mt, true);
+        else bias_max(sa, t, 0, 32, mt, false);
         const float off = bias_end(mt);
         if constexpr (!EARLY_VT) {
 #pragma unroll
-            for (int g = 0; g < NPV; ++g)
-                if (!HALF || g / DB < 2) vt_pair(g, buf);
+            for (int g = 0; g < NPV; ++g) vt_pair(g, buf);
         }
         WG_STAMP(1);
-        probs(sa, off, 0, NE);
+        probs(sa, off, 0, 32);
         WG_STAMP(2);
         // O^T += V^T . P^T  (operands of the asm reads above: wait for them here, fenced from the MFMAs)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int g = 0; g < NPV; ++g)
-            if (!HALF || g / DB < 2) pv_one(g);
+        for (int g = 0; g < NPV; ++g) pv_one(g);
         WG_STAMP(3);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         WG_STAMP(4);
-    };
-    if constexpr (HALF_LAST) {
-        for (int t = 0; t + 1 < nt; ++t) tile(t, std::false_type());
-        tile(nt - 1, std::true_type());
-    } else {
-        // (the same loop written out: instantiating it through the generic lambda above shifts hipcc's register allocation and one
-        // head_dim-128 variant starts to spill)
-        for (int t = 0; t < nt; ++t) {
-            const int buf = t & 1;
-            WG_STAMP(0);
-            if (t + 1 < nt) {
-                stage(t + 1, buf ^ 1, false);
-                stage(t + 1, buf ^ 1, true);
-            }
-            bias_begin(t);
-    #pragma unroll
-            for (int g = 0; g < NQK; ++g) qk_read(kv + buf * TILE2, g);
-    #pragma unroll
-            for (int g = 0; g < NQK; ++g) qk_one(sa, g);
-            // V^T fragments: inline-asm reads (invisible to hipcc's wait insertion), issued as early as the registers allow so that
-            // their LDS latency hides under the softmax: right behind the S^T MFMAs, or -- key-bias variants, whose bias row
-            // occupies 32 registers until it is applied -- after the running max.  Every LDS read hipcc does know about is retired
-            // first: its wait would cover these too.
-            constexpr bool EARLY_VT = !KB;
-            if constexpr (GRID) {
-    #pragma unroll
-                for (int i = 0; i < RPT; ++i) asm volatile("" : "+v"(rh[i]));
-            }
-            if constexpr (EARLY_VT) {
-    #pragma unroll
-                for (int g = 0; g < NPV; ++g) vt_pair(g, buf);
-            }
-            float mt = NEG_BIG;
-            if (ragged && t + 1 == nt) bias_max(sa, t, 0, 32, mt, true);
-            else bias_max(sa, t, 0, 32, mt, false);
-            const float off = bias_end(mt);
-            if constexpr (!EARLY_VT) {
-    #pragma unroll
-                for (int g = 0; g < NPV; ++g) vt_pair(g, buf);
-            }
-            WG_STAMP(1);
-            probs(sa, off, 0, 32);
-            WG_STAMP(2);
-            // O^T += V^T . P^T  (operands of the asm reads above: wait for them here, fenced from the MFMAs)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-    #pragma unroll
-            for (int g = 0; g < NPV; ++g) pv_one(g);
-            WG_STAMP(3);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            WG_STAMP(4);
-        }
     }
 
 #ifdef WG_ATTN_STAMP
@@ -634,7 +515,8 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_kernel(AttnArgs a) {
 // =====================================================================================================================================
 // Windowed attention (S <= 32: SAM's 14 x 14 windows), PERSISTENT form of wg_attn_kernel<HD, S, NW, false>.
 //
-// A window has 4 key tiles, and in-kernel stamps (tools/attn_window_stamps.py on the one-unit-per-workgroup kernel) put 40 % of a
+// A window has 4 key tiles, and in-kernel stamps (a -DWG_ATTN_STAMP build read by tools/attn_stamps.py, taken on the one-unit-per-workgroup
+// kernel this one replaced) put 40 % of a
 // workgroup's life BEFORE its first tile: waiting for the query rows / the first K, V tile from memory and building the rel-pos tables,
 // plus 7 % storing the output -- with one (ViT-H: 7 waves x 215 registers) or two workgroups per CU nothing else runs meanwhile.
 // Here a workgroup walks units (window, head, query chunk) bid, bid + grid, ...: the NEXT unit's query rows are requested when the
@@ -646,25 +528,17 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_kernel(AttnArgs a) {
 template <int HD, int S, int NW>
 __global__ __launch_bounds__(NW * 64, 2) void wg_attn_window_kernel(AttnArgs a, int total_units) {
     static_assert(S > 0 && S <= 32, "window sides up to 32 (padded rows of 16 / 32 slots)");
-    constexpr int HDP = (HD == 80) ? 96 : (HD == 16 ? 32 : HD);
-    constexpr int ROWB = (HD == 80) ? 208 : HDP * 2;
-    constexpr int ROWBV = (HD == 80) ? 192 : ROWB;
-    constexpr int TILE = 64 * ROWB, TILEV = 64 * ROWBV, TILE2 = TILE + TILEV;
-    constexpr int KSTEPS = HD / 16;
-    constexpr int DB = HDP / 32;
+    using G = AttnGeom<HD, S>;   // (attn_common.h: what each constant means)
+    constexpr int HDP = G::HDP, ROWB = G::ROWB, ROWBV = G::ROWBV, TILE = G::TILE, TILEV = G::TILEV, TILE2 = G::TILE2, KSTEPS = G::KSTEPS, DB = G::DB;
     constexpr int SS = S * S;
-    constexpr int RP = S <= 16 ? 16 : 32;
-    constexpr int RPT = 64 / RP;
-    constexpr int NTG = (S + RPT - 1) / RPT;
+    constexpr int RP = G::RP, RPT = G::RPT, NTG = G::NTG, SP = G::SP, NRW = G::NRW, RELROWS = G::RELROWS;
     static_assert(NTG % 2 == 0, "the next unit's first tile goes to buffer 0: an even number of tiles per unit");
-    constexpr int SP = NTG * RPT + 1;
-    constexpr int NRW = RP / 2;
+    constexpr AttnWindowLds L = wg_attn_window_lds<HD, S>(NW);
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* kv = smem;                                                  // [2 buffers][K tile | V tile]
-    float* tab = (float*)(smem + 2 * TILE2);                          // per-wave rel-pos table in key space
-    constexpr int RELROWS = 2 * S - 1;
-    bf16* rels = (bf16*)(tab + NW * 32 * SP);                         // rel_w | rel_h table rows [2][RELROWS][HD], once per workgroup
-    char* qslab = (char*)(rels + 2 * RELROWS * HD);                   // per wave: the NEXT unit's query fragments, KSTEPS x 1 KiB (LDS-DMA)
+    char* kv = smem + L.kv;                                           // [2 buffers][K tile | V tile]
+    float* tab = (float*)(smem + L.tab);                              // per-wave rel-pos table in key space
+    bf16* rels = (bf16*)(smem + L.rels);                              // rel_w | rel_h table rows [2][RELROWS][HD], once per workgroup
+    char* qslab = smem + L.qslab;                                     // per wave: the NEXT unit's query fragments, KSTEPS x 1 KiB (LDS-DMA)
     // head_dim 80 is out of registers (215 before the unit loop's state): the width term of the bias (C operand of a tile's first S^T MFMAs,
     // 16 registers) lives in a lane-private LDS row there and is read per tile
     constexpr bool RELW_LDS = (HD == 80);
@@ -673,7 +547,7 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_window_kernel(AttnArgs a, 
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ql_lane = lane & 31, hi = lane >> 5;
-    float* relw_lds = (float*)(qslab + NW * KSTEPS * 1024) + (wave * 64 + lane) * 20;   // 80-byte pitch: conflict-free b128 reads
+    float* relw_lds = (float*)(smem + L.relw) + (wave * 64 + lane) * 20;   // 80-byte pitch: conflict-free b128 reads
 
     // ---- a unit: (batch, window, head, query chunk) ---------------------------------------------------------------------------------
     struct Unit { int b, wy, wx, hcol, qh, qw, klim0, qvalid; long qrow; };
@@ -704,11 +578,6 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_window_kernel(AttnArgs a, 
         u.qvalid = (ql_raw < SS && inside) ? 1 : 0;
         u.qrow = (long)u.b * a.Hg * a.Hg + (inside ? gy * a.Hg + gx : 0);
         u.klim0 = S < a.Hg - u.wy * S ? S : a.Hg - u.wy * S;     // window rows that exist in the image
-    };
-    auto load_q = [&](const Unit& u, bf16x8 (&q)[KSTEPS]) __attribute__((always_inline)) {
-        const bf16* qp = a.Q + u.qrow * a.ldq + u.hcol + 8 * hi;
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) q[s] = *(const bf16x8*)(qp + 16 * s);
     };
     char* myq = qslab + wave * KSTEPS * 1024;
     auto dma_q = [&](const Unit& u) __attribute__((always_inline)) {      // the same fragments, global -> LDS without passing through registers
@@ -798,7 +667,7 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_window_kernel(AttnArgs a, 
     Unit cur;
     decode(blockIdx.x, cur);
     bf16x8 qf[KSTEPS];
-    load_q(cur, qf);
+    wg_attn_load_q<KSTEPS>(a, cur.qrow, cur.hcol, hi, qf);
     init_run(cur);
     stage(0, 0, false, cur);
     stage(0, 0, true, cur);
@@ -919,12 +788,7 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_window_kernel(AttnArgs a, 
                 const int ks = g / DB, d = g % DB;
                 if (HALF && ks >= 2) continue;
                 const unsigned ad = vt_ad[d] + (unsigned)(buf * TILE2);
-                switch (ks) {
-                    case 0: vt[0][d][0] = wg_ds_read_tr<0 * 16 * ROWBV>(ad); vt[0][d][1] = wg_ds_read_tr<0 * 16 * ROWBV + 8 * ROWBV>(ad); break;
-                    case 1: vt[1][d][0] = wg_ds_read_tr<1 * 16 * ROWBV>(ad); vt[1][d][1] = wg_ds_read_tr<1 * 16 * ROWBV + 8 * ROWBV>(ad); break;
-                    case 2: vt[2][d][0] = wg_ds_read_tr<2 * 16 * ROWBV>(ad); vt[2][d][1] = wg_ds_read_tr<2 * 16 * ROWBV + 8 * ROWBV>(ad); break;
-                    default: vt[3][d][0] = wg_ds_read_tr<3 * 16 * ROWBV>(ad); vt[3][d][1] = wg_ds_read_tr<3 * 16 * ROWBV + 8 * ROWBV>(ad); break;
-                }
+                wg_attn_vt_pair<ROWBV>(ks, ad, vt[ks][d]);
             }
             // height term + running max
             float mt = NEG_BIG;
@@ -1003,11 +867,7 @@ __global__ __launch_bounds__(NW * 64, 2) void wg_attn_window_kernel(AttnArgs a, 
 
 template <int HD, int S, int NW>
 static int launch_attn_window(const AttnArgs& a, int groups, hipStream_t st) {
-    constexpr int TILE = 64 * ((HD == 80) ? 208 + 192 : 4 * (HD == 16 ? 32 : HD));
-    constexpr int RP = S <= 16 ? 16 : 32;
-    constexpr int RPT = 64 / RP;
-    constexpr int SP = ((S + RPT - 1) / RPT) * RPT + 1;
-    const size_t lds = 2 * TILE + (size_t)NW * 32 * SP * 4 + 2 * (2 * S - 1) * HD * 2 + (size_t)NW * (HD / 16) * 1024 + (HD == 80 ? (size_t)NW * 64 * 80 : 0);
+    constexpr size_t lds = wg_attn_window_lds<HD, S>(NW).total;
     static WgPerDevice once;
     static int per_cu_of[64] = {};
     int dev = 0;
@@ -1036,13 +896,7 @@ static int launch_attn_window(const AttnArgs& a, int groups, hipStream_t st) {
 
 template <int HD, int S, int NW, bool KB>
 static int launch_attn_impl(const AttnArgs& a, int groups, hipStream_t st) {
-    constexpr int TILE = 64 * ((HD == 80) ? 208 + 192 : 4 * (HD == 16 ? 32 : HD));   // bytes of a K tile + a V tile (head_dim 80: 208- and 192-byte rows)
-    constexpr int RP = S <= 16 ? 16 : (S <= 32 ? 32 : 64);
-    constexpr int RPT = 64 / RP;
-    constexpr int SP = S > 0 ? ((S + RPT - 1) / RPT) * RPT + 1 : 1;
-    size_t lds = 2 * TILE;
-    if (S > 0) lds += (size_t)NW * 32 * SP * 4;
-    else lds += (size_t)((a.Lk + 63) / 64) * 64 * 4;
+    size_t lds = wg_attn_lds<HD, S>(NW, a.Lk).total;
     if (lds > 160 * 1024) {
         wg_set_error("attention: LDS request %zu exceeds 160 KiB", lds);
         return WG_ERR_UNSUPPORTED;

@@ -1,4 +1,5 @@
-// Shared by attn.hip and attn_pipe.hip: argument block, LDS swizzles of the K / V tiles, the asm form of the transposed LDS read.
+// Shared by attn.hip, attn_window_unit.hip and attn_pipe.hip: argument block, LDS swizzles of the K / V tiles, tile geometry and LDS layouts,
+// the asm form of the transposed LDS read, the few device pieces the kernels share.
 #pragma once
 #include "wg_common.h"
 
@@ -36,6 +37,68 @@ template <int HD> __device__ __forceinline__ int swzV(int row) {
     return 0;
 }
 
+// ---- tile geometry: stated once for the kernels of attn.hip / attn_window_unit.hip and their launchers -------------------------------
+// S == 0: plain attention; S > 0: the side of a SAM window or (S == 64) of the global grid.
+template <int HD, int S> struct AttnGeom {
+    static constexpr int HDP = (HD == 80) ? 96 : (HD == 16 ? 32 : HD);  // head dim padded to a multiple of 32 inside LDS
+    // head_dim 80: rows padded once more to 13 chunks = 52 dwords, a pitch that sends 16 consecutive rows to 16 different bank
+    // quads (the K fragment reads of 192-byte rows were 4-way conflicted: rows r and r + 4 shared their banks); the 13th chunk of
+    // a row is never read
+    static constexpr int ROWB = (HD == 80) ? 208 : HDP * 2;   // bytes per K row
+    // V rows of head_dim 80 keep the natural 192-byte pitch (12 chunks): four consecutive rows x 16 dwords then fall on disjoint bank
+    // ranges for the transposed reads (pitch 48 dwords: 0, 48, 32, 16 mod 64), which the 208-byte pitch of the K rows (0, 52, 40, 28: rows
+    // r and r + 1 overlap by four banks, a 2-way conflict) does not give; K keeps 208 for its ds_read_b128 pattern
+    static constexpr int ROWBV = (HD == 80) ? 192 : ROWB;     // bytes per V row
+    static constexpr int TILE = 64 * ROWB;        // bytes per K tile
+    static constexpr int TILEV = 64 * ROWBV;      // bytes per V tile
+    static constexpr int TILE2 = TILE + TILEV;    // one buffer = K tile | V tile
+    static constexpr int KSTEPS = HD / 16;        // QK^T runs over the real head dim only
+    static constexpr int DB = HDP / 32;           // PV d-blocks; columns >= HD hold don't-care data and are never stored
+    // Grid mode key order: window rows padded to RP slots (16 / 32 / 64), RPT rows per 64-key tile.  A key slot's
+    // column (kw) then depends only on the accumulator register, its row (kh) only on (tile, register): the width term
+    // of the rel-pos bias is RP/2 registers per lane, the height term RPT LDS reads per tile, and padding slots are
+    // masked by -inf entries in those two tables instead of per-element tests.  (S == 64: a tile is exactly one grid row.)
+    static constexpr int RP = S <= 16 ? 16 : (S <= 32 ? 32 : 64);
+    static constexpr int RPT = 64 / RP;
+    static constexpr int NTG = S > 0 ? (S + RPT - 1) / RPT : 0;   // key tiles per window
+    static constexpr int SP = S > 0 ? NTG * RPT + 1 : 1;          // relh table row (fp32 words, odd => conflict-free)
+    static constexpr int NRW = S > 0 ? RP / 2 : 1;                // width-bias registers per lane
+    static constexpr int RELROWS = 2 * S - 1;                     // rows of a rel-pos table
+};
+
+// ---- dynamic LDS of each kernel: section offsets (bytes) and the total.  The kernel carves its pointers from it, the launcher requests
+// `total` -- the two cannot disagree.
+// wg_attn_kernel<HD, S, NW, KB>:  kv [2 buffers][K tile | V tile] | tab (grid: per-wave rel-pos table; plain: the key bias row, whole tiles of Lk)
+struct AttnLds { size_t kv, tab, total; };
+template <int HD, int S> constexpr AttnLds wg_attn_lds(int nw, int Lk) {
+    using G = AttnGeom<HD, S>;
+    const size_t tab = 2 * G::TILE2;
+    return {0, tab, tab + (S > 0 ? (size_t)nw * 32 * G::SP * 4 : (size_t)((Lk + 63) / 64) * 64 * 4)};
+}
+// wg_attn_window_kernel<HD, S, NW>:  kv | tab (per-wave rel-pos table in key space) | rels (rel_w | rel_h rows [2][RELROWS][HD]) |
+// qslab (per wave: the next unit's query fragments, KSTEPS x 1 KiB) | relw (head_dim 80: a lane-private row of the width term, 80-byte pitch)
+struct AttnWindowLds { size_t kv, tab, rels, qslab, relw, total; };
+template <int HD, int S> constexpr AttnWindowLds wg_attn_window_lds(int nw) {
+    using G = AttnGeom<HD, S>;
+    const size_t tab = 2 * G::TILE2, rels = tab + (size_t)nw * 32 * G::SP * 4, qslab = rels + 2 * G::RELROWS * HD * 2;
+    const size_t relw = qslab + (size_t)nw * G::KSTEPS * 1024;
+    return {0, tab, rels, qslab, relw, relw + (HD == 80 ? (size_t)nw * 64 * 80 : 0)};
+}
+// wg_attn_window_unit_kernel<HD, S, NW>:  kv [2 units][NTG tiles][K tile | V tile] | tab | rels
+struct AttnWindowUnitLds { size_t kv, tab, rels, total; };
+template <int HD, int S> constexpr AttnWindowUnitLds wg_attn_window_unit_lds(int nw) {
+    using G = AttnGeom<HD, S>;
+    const size_t tab = 2 * G::NTG * G::TILE2, rels = tab + (size_t)nw * 32 * G::SP * 4;
+    return {0, tab, rels, rels + 2 * G::RELROWS * HD * 2};
+}
+// the bytes each compiled combination requests (occupancy follows from them: a change here is a change of a launch)
+static_assert(wg_attn_window_lds<64, 14>(4).total == 64768 && wg_attn_window_lds<64, 32>(8).total == 115456 && wg_attn_window_lds<32, 14>(7).total == 49408 &&
+              wg_attn_window_lds<32, 28>(5).total == 52224 && wg_attn_window_lds<80, 14>(7).total == 146752, "window kernel LDS");
+static_assert(wg_attn_lds<64, 64>(8, 0).total == 99328 && wg_attn_lds<80, 64>(8, 0).total == 117760, "global kernel LDS");
+static_assert(wg_attn_lds<16, 0>(1, 1025).total == 20736 && wg_attn_lds<32, 0>(4, 1025).total == 20736 && wg_attn_lds<64, 0>(4, 1025).total == 37120 &&
+              wg_attn_lds<128, 0>(8, 1025).total == 69888, "plain kernel LDS: two buffers + four bytes per key of the whole tiles");
+static_assert(wg_attn_window_unit_lds<64, 14>(7).total == 153216, "unit kernel LDS");
+
 // raw v_exp_f32: exp2f() adds a denormal-range fix-up (compare, select, ldexp) around it that triples the cost of the
 // one instruction softmax cannot avoid; arguments here are <= RESCALE_THR and results below 2^-126 may flush to zero.
 __device__ __forceinline__ float wg_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
@@ -50,6 +113,30 @@ template <int OFF> __device__ __forceinline__ u32x2 wg_ds_read_tr(unsigned lds_a
     return v;
 }
 
+
+// ---- device pieces the kernels of attn.hip and attn_window_unit.hip have in common --------------------------------------------------------
+// Only these two: hipcc's register allocation of these kernels shifts when their code is reshaped, and moving the unit decode, the staging
+// set-up, the V^T address set-up, the rel-pos pass or the epilogue store out of the kernels changed their instruction streams
+// (tools/isa_fingerprint.py against the commit before tells); those stay written out in each kernel.
+
+// this lane's query row as the B operand of the S^T MFMAs: its half (hi) of every 16 head dims
+template <int KSTEPS>
+__device__ __forceinline__ void wg_attn_load_q(const AttnArgs& a, long qrow, int hcol, int hi, bf16x8 (&q)[KSTEPS]) {
+    const bf16* qp = a.Q + qrow * a.ldq + hcol + 8 * hi;
+#pragma unroll
+    for (int s = 0; s < KSTEPS; ++s) q[s] = *(const bf16x8*)(qp + 16 * s);
+}
+
+// the two transposed reads (key rows 16 ks + .. and + 8) of k-step ks behind a lane's V^T address, i.e. the operands of one P.V MFMA
+// (the offset must be an immediate: switch on the unrolled ks)
+template <int ROWBV> __device__ __forceinline__ void wg_attn_vt_pair(int ks, unsigned ad, u32x2 (&v)[2]) {
+    switch (ks) {
+        case 0: v[0] = wg_ds_read_tr<0 * 16 * ROWBV>(ad); v[1] = wg_ds_read_tr<0 * 16 * ROWBV + 8 * ROWBV>(ad); break;
+        case 1: v[0] = wg_ds_read_tr<1 * 16 * ROWBV>(ad); v[1] = wg_ds_read_tr<1 * 16 * ROWBV + 8 * ROWBV>(ad); break;
+        case 2: v[0] = wg_ds_read_tr<2 * 16 * ROWBV>(ad); v[1] = wg_ds_read_tr<2 * 16 * ROWBV + 8 * ROWBV>(ad); break;
+        default: v[0] = wg_ds_read_tr<3 * 16 * ROWBV>(ad); v[1] = wg_ds_read_tr<3 * 16 * ROWBV + 8 * ROWBV>(ad); break;
+    }
+}
 
 // attn_pipe.hip: the software-pipelined kernel for head_dim 64 (SAM global attention, CLIP without a key mask)
 bool wg_attn_pipe_takes(const AttnArgs& a, int head_dim, int S, int nw);

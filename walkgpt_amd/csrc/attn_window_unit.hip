@@ -19,34 +19,22 @@
 template <int HD, int S, int NW>
 __global__ __launch_bounds__(NW * 64) void wg_attn_window_unit_kernel(AttnArgs a, int total_units) {
     static_assert(S > 0 && S <= 32, "window sides up to 32 (padded rows of 16 / 32 slots)");
-    constexpr int HDP = (HD == 80) ? 96 : (HD == 16 ? 32 : HD);
-    constexpr int ROWB = (HD == 80) ? 208 : HDP * 2;
-    constexpr int ROWBV = (HD == 80) ? 192 : ROWB;
-    constexpr int TILE = 64 * ROWB, TILEV = 64 * ROWBV, TILE2 = TILE + TILEV;
-    constexpr int KSTEPS = HD / 16;
-    constexpr int DB = HDP / 32;
+    static_assert(HD == 64, "two units of K / V in LDS and the width term in registers: head_dim 64 (others: wg_attn_window_kernel)");
+    using G = AttnGeom<HD, S>;   // (attn_common.h: what each constant means)
+    constexpr int ROWB = G::ROWB, ROWBV = G::ROWBV, TILE = G::TILE, TILEV = G::TILEV, TILE2 = G::TILE2, KSTEPS = G::KSTEPS, DB = G::DB;
     constexpr int SS = S * S;
-    constexpr int RP = S <= 16 ? 16 : 32;
-    constexpr int RPT = 64 / RP;
-    constexpr int NTG = (S + RPT - 1) / RPT;
-    constexpr int SP = NTG * RPT + 1;
-    constexpr int NRW = RP / 2;
+    constexpr int RP = G::RP, RPT = G::RPT, NTG = G::NTG, SP = G::SP, NRW = G::NRW, RELROWS = G::RELROWS;
+    constexpr AttnWindowUnitLds L = wg_attn_window_unit_lds<HD, S>(NW);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int UNIT = NTG * TILE2;                                 // all K / V tiles of one (window, head)
-    char* kv = smem;                                                  // [2 units][NTG tiles][K tile | V tile]
-    float* tab = (float*)(smem + 2 * UNIT);                           // per-wave rel-pos table in key space
-    constexpr int RELROWS = 2 * S - 1;
-    bf16* rels = (bf16*)(tab + NW * 32 * SP);                         // rel_w | rel_h table rows [2][RELROWS][HD], once per workgroup
-    char* qslab = (char*)(rels + 2 * RELROWS * HD);                   // (head_dim 80 only: the lane-private width-term rows live behind the tables)
-    // head_dim 80 is out of registers (215 before the unit loop's state): the width term of the bias (C operand of a tile's first S^T MFMAs,
-    // 16 registers) lives in a lane-private LDS row there and is read per tile
-    constexpr bool RELW_LDS = (HD == 80);
+    char* kv = smem + L.kv;                                           // [2 units][NTG tiles][K tile | V tile]
+    float* tab = (float*)(smem + L.tab);                              // per-wave rel-pos table in key space
+    bf16* rels = (bf16*)(smem + L.rels);                              // rel_w | rel_h table rows [2][RELROWS][HD], once per workgroup
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ql_lane = lane & 31, hi = lane >> 5;
-    float* relw_lds = (float*)qslab + (wave * 64 + lane) * 20;   // 80-byte pitch: conflict-free b128 reads
 
     // ---- a unit: (batch, window, head, query chunk) ---------------------------------------------------------------------------------
     struct Unit { int b, wy, wx, hcol, qh, qw, klim0, qvalid; long qrow; };
@@ -78,11 +66,6 @@ __global__ __launch_bounds__(NW * 64) void wg_attn_window_unit_kernel(AttnArgs a
         u.qrow = (long)u.b * a.Hg * a.Hg + (inside ? gy * a.Hg + gx : 0);
         u.klim0 = S < a.Hg - u.wy * S ? S : a.Hg - u.wy * S;     // window rows that exist in the image
     };
-    auto load_q = [&](const Unit& u, bf16x8 (&q)[KSTEPS]) __attribute__((always_inline)) {
-        const bf16* qp = a.Q + u.qrow * a.ldq + u.hcol + 8 * hi;
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) q[s] = *(const bf16x8*)(qp + 16 * s);
-    };
     // rel-pos table rows: the same for every unit -> LDS, once per workgroup (held in registers they cost 32 - 40 VGPRs across the unit loop)
     constexpr int NJB = (RELROWS + 31) / 32;
     for (int i = tid; i < 2 * RELROWS * HD / 8; i += NW * 64) {
@@ -107,8 +90,7 @@ __global__ __launch_bounds__(NW * 64) void wg_attn_window_unit_kernel(AttnArgs a
                 const int ii = wave + i * NW < ninst ? wave + i * NW : ninst - 1;
                 const int ci = ii * 64 + lane;
                 const int row = ci / cpr, cs = ci % cpr;
-                int c = cs ^ (o ? swzV<HD>(row) : swzK<HD>(row));
-                if (HDP != HD && c * 8 >= HD) c = HD / 8 - 1;
+                const int c = cs ^ (o ? swzV<HD>(row) : swzK<HD>(row));
                 coff[o][i] = c * 8;
                 int kw = row % RP;
                 kw = kw < S ? kw : S - 1;
@@ -171,12 +153,11 @@ __global__ __launch_bounds__(NW * 64) void wg_attn_window_unit_kernel(AttnArgs a
             stage(t, ubuf, true, u);
         }
     };
-    static_assert(HDP == HD, "head_dim 64 / 32 / 128: every (d, g4) piece of the output exists");
     const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(a.O, 0, (int)((long)a.B * a.Hg * a.Hg * a.ldo * 2), WG_RSRC_FLAGS);
     Unit cur;
     decode(blockIdx.x, cur);
     bf16x8 qf[KSTEPS], qn[KSTEPS];
-    load_q(cur, qn);
+    wg_attn_load_q<KSTEPS>(a, cur.qrow, cur.hcol, hi, qn);
     stage_unit(0, cur);
     int ub = 0;
 
@@ -198,12 +179,11 @@ __global__ __launch_bounds__(NW * 64) void wg_attn_window_unit_kernel(AttnArgs a
             Unit nxt;
             decode(nbid, nxt);
             stage_unit(ub ^ 1, nxt);
-            load_q(nxt, qn);
+            wg_attn_load_q<KSTEPS>(a, nxt.qrow, nxt.hcol, hi, qn);
         }
 
         // ---- rel-pos tables of this unit's queries: T^T = Rel . Q^T by MFMA, scattered to key space (wave-private LDS) --------------------
         f32x16 relw_c;
-        (void)relw_c;
         auto rel_pass = [&](int which) __attribute__((always_inline)) {
             const int qpos = which == 0 ? cur.qw : cur.qh;
             for (int k = S + hi; k < SP; k += 2) mytab[ql_lane * SP + k] = NEG_BIG;
@@ -233,9 +213,7 @@ __global__ __launch_bounds__(NW * 64) void wg_attn_window_unit_kernel(AttnArgs a
         for (int e = 0; e < 16; ++e) {
             const int j = e % NRW;
             const int kw = (j & 3) + 8 * (j >> 2) + 4 * hi;
-            const float wv = (kw < S ? mytab[ql_lane * SP + kw] : NEG_BIG) * inv_sc2;
-            if constexpr (RELW_LDS) relw_lds[e] = wv;
-            else relw_c[e] = wv;
+            relw_c[e] = (kw < S ? mytab[ql_lane * SP + kw] : NEG_BIG) * inv_sc2;
         }
         asm volatile("" ::: "memory");
         rel_pass(1);
@@ -273,19 +251,7 @@ __global__ __launch_bounds__(NW * 64) void wg_attn_window_unit_kernel(AttnArgs a
             for (int g = 0; g < NQK; ++g) {
                 if (HALF && (g & 1)) continue;
                 const int kb = g & 1, s = g >> 1;
-                if (s == 0) {                 // (+ width term of the bias: C operand)
-                    if constexpr (RELW_LDS) {
-                        f32x16 wc;
-#pragma unroll
-                        for (int q4 = 0; q4 < 4; ++q4) {
-                            const f32x4 w4 = *(const f32x4*)(relw_lds + 4 * q4);
-                            wc[4 * q4] = w4[0]; wc[4 * q4 + 1] = w4[1]; wc[4 * q4 + 2] = w4[2]; wc[4 * q4 + 3] = w4[3];
-                        }
-                        sa[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[g], qf[s], wc, 0, 0, 0);
-                    } else {
-                        sa[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[g], qf[s], relw_c, 0, 0, 0);
-                    }
-                }
+                if (s == 0) sa[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[g], qf[s], relw_c, 0, 0, 0);   // (+ width term of the bias: C operand)
                 else sa[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[g], qf[s], sa[kb], 0, 0, 0);
             }
 #pragma unroll
@@ -296,12 +262,7 @@ __global__ __launch_bounds__(NW * 64) void wg_attn_window_unit_kernel(AttnArgs a
                 const int ks = g / DB, d = g % DB;
                 if (HALF && ks >= 2) continue;
                 const unsigned ad = vt_ad[d] + (unsigned)(ub * UNIT + buf * TILE2);
-                switch (ks) {
-                    case 0: vt[0][d][0] = wg_ds_read_tr<0 * 16 * ROWBV>(ad); vt[0][d][1] = wg_ds_read_tr<0 * 16 * ROWBV + 8 * ROWBV>(ad); break;
-                    case 1: vt[1][d][0] = wg_ds_read_tr<1 * 16 * ROWBV>(ad); vt[1][d][1] = wg_ds_read_tr<1 * 16 * ROWBV + 8 * ROWBV>(ad); break;
-                    case 2: vt[2][d][0] = wg_ds_read_tr<2 * 16 * ROWBV>(ad); vt[2][d][1] = wg_ds_read_tr<2 * 16 * ROWBV + 8 * ROWBV>(ad); break;
-                    default: vt[3][d][0] = wg_ds_read_tr<3 * 16 * ROWBV>(ad); vt[3][d][1] = wg_ds_read_tr<3 * 16 * ROWBV + 8 * ROWBV>(ad); break;
-                }
+                wg_attn_vt_pair<ROWBV>(ks, ad, vt[ks][d]);
             }
             // height term + running max
             float mt = NEG_BIG;
@@ -349,7 +310,6 @@ __global__ __launch_bounds__(NW * 64) void wg_attn_window_unit_kernel(AttnArgs a
             for (int t = 0; t < NTG; ++t) tile(t, std::false_type());
         }
 
-        // ---- O = O^T / l, 8-byte stores ------------------------------------------------------------------------------------------------
         // ---- O = O^T / l, 8-byte stores.  (Buffer stores: query slots outside the window or the image leave through an out-of-range offset, no
         // exec-mask branch around the stores.)  Tried and not kept: holding the packed output in registers and storing it behind the NEXT
         // unit's requests, so that the wait at the head of the loop finds no young stores to drain -- 97 us per launch against 88.
@@ -383,8 +343,7 @@ bool wg_attn_window_unit_takes(const AttnArgs& a) { return (long)a.B * a.Hg * a.
 
 int wg_attn_window_unit_launch(AttnArgs a, int groups, hipStream_t st) {
     constexpr int HD = 64, S = 14, NW = 7;
-    constexpr int TILE2 = 64 * 4 * HD, RPT = 4, NTG = (S + RPT - 1) / RPT, SP = NTG * RPT + 1;
-    constexpr size_t lds = 2 * NTG * TILE2 + (size_t)NW * 32 * SP * 4 + 2 * (2 * S - 1) * HD * 2;
+    constexpr size_t lds = wg_attn_window_unit_lds<HD, S>(NW).total;
     static_assert(lds <= 160 * 1024, "two units of K / V tiles + the rel-pos tables in one CU's LDS");
     static WgPerDevice once;
     int dev = 0;
