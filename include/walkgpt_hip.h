@@ -452,6 +452,15 @@ int wg_f32_mha_ex(const float* q, long ldq, const float* k, const float* v, long
  * 0 none, 1 (default) SAM global attention on a 64 x 64 grid (image_encoder.py:235-260 with window_size 0), 2 also plain attention without a key
  * bias on whole 64-key tiles.  Returns the previous mode; a negative argument only queries.  Process-wide, not per stream. */
 int wg_attn_pipe_mode(int mode);
+/* Which kernel wg_mha_bf16 / wg_sam_attn_relpos_bf16 run for a shape, decided by the code the launchers themselves use (csrc/attn.hip), under the
+ * current wg_attn_pipe_mode; host arithmetic only, no GPU needed.  The answer is
+ *     family * 10000000 + head_dim * 10000 + S * 100 + waves * 10 + key_bias
+ * family 1: wg_attn_kernel<head_dim, S, waves, key_bias> (S = 0 plain attention, 64 the global grid), 2: wg_attn_window_kernel<head_dim, S, waves>,
+ * 3: wg_attn_window_unit_kernel<64, 14, 7>, 4: wg_attn_pipe_kernel<S, waves> (head_dim 64); S the window side, waves per workgroup, key_bias 0 / 1.
+ * E.g. 10640040 = wg_attn_kernel<64, 0, 4, false>, 40646480 = the pipelined kernel on the 64 x 64 grid.  Negative: no compiled kernel (-2) or a
+ * bad shape (-1).  wg_mha_route does not know about wg_mha_small_bf16: the caller chooses between the two entry points. */
+int wg_mha_route(int head_dim, int Lq, int Lk, int has_key_bias);
+int wg_sam_attn_route(int B, int grid, int window, int heads, int head_dim);
 /* Test support: writes `pattern` over the first 64 KiB of every compute unit's LDS (2048 workgroups; sink: one device word, or NULL).  LDS is not
  * cleared between launches, so a kernel that reads a word it never wrote sees whatever ran before it; tests poison with NaN bits first. */
 int wg_debug_fill_lds_u32(unsigned pattern, void* sink, void* stream);

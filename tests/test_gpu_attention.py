@@ -180,8 +180,9 @@ def pipe_plain():
 
 @pytest.mark.parametrize("B,Lq,Lk,heads", [(1, 4096, 4096, 2), (2, 1024, 1024, 2), (1, 300, 1025, 3), (1, 512, 256, 2)])
 def test_mha_pipelined_loop(dev, B, Lq, Lk, heads, pipe_plain):
-    """head_dim 64 without a key bias on whole 64-key tiles: the software-pipelined kernel (attn_pipe.hip; eight-wave and four-wave
-    workgroups, with and without the lone 1025th key, the shortest loop it takes)."""
+    """head_dim 64 without a key bias on whole 64-key tiles: the software-pipelined kernel (attn_pipe.hip; four-wave workgroups only -- the
+    wave-count choice of wg_mha_bf16 never picks eight at head_dim 64, so wg_attn_pipe_kernel<0, 8> is not reachable from here --, with and
+    without the lone 1025th key, the shortest loop it takes)."""
     hd = 64
     D = heads * hd
     q, k, v = _rand((B, Lq, D), 31), _rand((B, Lk, D), 32), _rand((B, Lk, D), 33)

@@ -144,6 +144,8 @@ _SPECIAL = {"wg_last_error": (ctypes.c_char_p, []), "wg_version": (c_int, []),
             "wg_colsum_det_workspace_floats": (c_long, [c_int, c_int]),
             "wg_attn_bwd_workspace_floats": (c_long, [c_int, c_int, c_int, c_int, c_int]),
             "wg_sam_attn_mx_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+            "wg_mha_route": (c_int, [c_int, c_int, c_int, c_int]),
+            "wg_sam_attn_route": (c_int, [c_int, c_int, c_int, c_int, c_int]),
             "wg_gemm_pick_tile": (c_int, [c_int, c_int]),
             "wg_gemm_ln_supported": (c_int, [c_int, c_int, c_int, c_long, c_long, c_long]),
             "wg_gemm_row_partials_supported": (c_int, [c_int, c_int, c_int, c_long, c_long, c_long]),

@@ -8,6 +8,11 @@
 //                                    64 -> 70 zero padding whose pad tokens carry q = k = v = qkv-bias and take part in the softmax as keys.
 //   head_dim 64, windows of 14     : wg_attn_window_unit_kernel<64, 14, 7> (attn_window_unit.hip), a whole (window, head) of K / V ahead.
 //   head_dim 64, global and, where wg_attn_pipe_takes() says so, plain: wg_attn_pipe_kernel (attn_pipe.hip), the hand-placed loop.
+// Which of them a call takes is decided in one place per entry point (wg_mha_route_of, wg_sam_route_of below) and can be asked without
+// running anything: wg_mha_route / wg_sam_attn_route.
+// Compiled, not reachable from the entry point: wg_attn_kernel<64, 0, 8, *>, wg_attn_kernel<32, 0, 8, *> and wg_attn_pipe_kernel<0, 8>.  At
+//   head_dim <= 64 the wave-count choice scores eight waves at 0.95 x their query-slot utilisation and four waves at 1.0 x theirs, and
+//   rounding the query blocks up to a multiple of four never wastes more than rounding them up to a multiple of eight, so eight never win.
 // The tile geometry and each kernel's LDS layout are stated once, in attn_common.h (AttnGeom, *Lds), for kernels and launchers alike.
 // window_partition / window_unpartition are pure address arithmetic here (no copies): keys and queries are fetched
 // from / written to their natural [B*H*W, 3D] / [B*H*W, D] rows.
@@ -917,23 +922,35 @@ static int launch_attn(const AttnArgs& a, int groups, hipStream_t st) {
     return launch_attn_impl<HD, S, NW, false>(a, groups, st);
 }
 
-// Plain multi-head attention (optionally cross attention, optionally with an additive per-key bias).
-// Q rows: (b*q_rows_per_batch + i), head h at columns [h*hd, (h+1)*hd); same for K, V, O.
-extern "C" int wg_mha_bf16(const void* Q, long ldq, long q_rows_per_batch, const void* K, long ldk, const void* V, long ldv,
-                           long k_rows_per_batch, void* O, long ldo, long o_rows_per_batch, const float* key_bias,
-                           int B, int heads, int head_dim, int Lq, int Lk, float scale, void* stream) {
-    WG_REQUIRE(Q && K && V && O, "mha: null operand");
-    WG_REQUIRE(B > 0 && heads > 0 && Lq > 0 && Lk > 0, "mha: bad shape");
-    WG_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0, "mha: leading dimensions must be multiples of 8");
-    WG_REQUIRE((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V) & 15) == 0 && ((uintptr_t)O & 7) == 0, "mha: misaligned operand");
-    AttnArgs a{};
-    a.Q = (const bf16*)Q; a.K = (const bf16*)K; a.V = (const bf16*)V; a.O = (bf16*)O;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
-    a.q_bs = q_rows_per_batch; a.k_bs = k_rows_per_batch; a.o_bs = o_rows_per_batch;
-    a.key_bias = key_bias; a.B = B; a.heads = heads; a.Lq = Lq; a.Lk = Lk; a.scale = scale;
-    hipStream_t st = (hipStream_t)stream;
-    const int groups = B * heads;
-    const int qblocks = (Lq + 31) / 32;
+// ---- routes: which kernel an entry point runs for a shape --------------------------------------------------------------------------
+// One function per entry point decides (wg_mha_route_of, wg_sam_route_of); the launchers below dispatch on its answer and the public
+// queries wg_mha_route / wg_sam_attn_route return it, so a test can assert the kernel a call takes.  The code (walkgpt_hip.h) is
+//   family * 10^7 + head_dim * 10^4 + S * 100 + waves * 10 + key bias      e.g. 10640040 = wg_attn_kernel<64, 0, 4, false>
+// and negative for "no compiled kernel".
+enum { WG_ROUTE_TILED = 1, WG_ROUTE_WINDOW = 2, WG_ROUTE_WINDOW_UNIT = 3, WG_ROUTE_PIPE = 4 };
+static constexpr int wg_route(int family, int hd, int S, int nw, bool kb) { return family * 10000000 + hd * 10000 + S * 100 + nw * 10 + (kb ? 1 : 0); }
+static constexpr int wg_route_family(int route) { return route / 10000000; }
+static constexpr int wg_route_nw(int route) { return route / 10 % 10; }
+
+// the <head_dim, waves> of plain wg_attn_kernel and the <head_dim, window, waves> of SAM attention that are compiled (each with and without
+// the key bias in plain mode); the route functions and the launchers both expand these lists
+#define WG_MHA_KERNELS(X)                                      \
+    X(64, 8) X(64, 4) X(64, 3) X(64, 1)                        \
+    X(128, 8) X(128, 4) X(128, 1)                              \
+    X(32, 8) X(32, 4) X(32, 1)                                 \
+    X(16, 1)
+#define WG_SAM_KERNELS(X)                                                                                                            \
+    X(64, 14, 4)   /* two 4-wave workgroups per window (one idle query slot in eight) measured 5 % faster than one of 7 waves */     \
+    X(64, 64, 8)                                                                                                                     \
+    X(64, 32, 8)                                                                                                                     \
+    X(32, 14, 7)                                                                                                                     \
+    X(32, 28, 5)                                                                                                                     \
+    X(80, 14, 7)   /* (two 4-wave workgroups per window: 166.8 vs 160.6 us at B = 8, 16 heads) */                                    \
+    X(80, 64, 8)
+
+// plain attention: a.Lq, a.Lk, a.key_bias
+static int wg_mha_route_of(const AttnArgs& a, int head_dim) {
+    const int qblocks = (a.Lq + 31) / 32;
     // waves per workgroup: query-slot utilisation x a measured per-size factor (tools/bench_attn.py, 4096 and 1025 keys).  At head_dim
     // <= 64 four-wave workgroups (three or more of them per CU) beat one eight-wave workgroup by 5 % and three-wave ones by 13 %
     // even at 1025 queries, where they leave 11 % of the query slots empty (CLIP: 67 -> 58 us); at head_dim 128 eight waves win.
@@ -950,16 +967,63 @@ extern "C" int wg_mha_bf16(const void* Q, long ldq, long q_rows_per_batch, const
             if (score > best + 1e-9) { best = score; nw = c; }
         }
     }
-    a.qchunks = (qblocks + nw - 1) / nw;
-    if (wg_attn_pipe_takes(a, head_dim, 0, nw)) return wg_attn_pipe_launch(a, 0, nw, st);   // head_dim 64, no key bias, whole tiles: the pipelined loop
-#define WG_MHA_CASE(HD_, NW_) if (head_dim == HD_ && nw == NW_) return launch_attn<HD_, 0, NW_>(a, groups, st);
-    WG_MHA_CASE(64, 8) WG_MHA_CASE(64, 4) WG_MHA_CASE(64, 3) WG_MHA_CASE(64, 1)
-    WG_MHA_CASE(128, 8) WG_MHA_CASE(128, 4) WG_MHA_CASE(128, 1)
-    WG_MHA_CASE(32, 8) WG_MHA_CASE(32, 4) WG_MHA_CASE(32, 1)
-    WG_MHA_CASE(16, 1)
-#undef WG_MHA_CASE
-    wg_set_error("mha: head_dim %d with %d query blocks not supported (32, 64, 128; 16 for <= 32 queries)", head_dim, qblocks);
+    if (wg_attn_pipe_takes(a, head_dim, 0, nw)) return wg_route(WG_ROUTE_PIPE, 64, 0, nw, false);
+#define WG_MHA_ROUTE(HD_, NW_) if (head_dim == HD_ && nw == NW_) return wg_route(WG_ROUTE_TILED, HD_, 0, NW_, a.key_bias != nullptr);
+    WG_MHA_KERNELS(WG_MHA_ROUTE)
+#undef WG_MHA_ROUTE
     return WG_ERR_UNSUPPORTED;
+}
+
+// SAM attention: a.B, a.heads, a.Hg, a.nW, a.ldo
+static int wg_sam_route_of(const AttnArgs& a, int head_dim, int window) {
+#define WG_SAM_ROUTE(HD_, S_, NW_)                                                                                      \
+    if (head_dim == HD_ && window == S_) {                                                                              \
+        if (S_ == 64 && wg_attn_pipe_takes(a, head_dim, S_, NW_)) return wg_route(WG_ROUTE_PIPE, 64, 64, 8, false);     \
+        if (HD_ == 64 && S_ == 14 && wg_attn_window_unit_takes(a)) return wg_route(WG_ROUTE_WINDOW_UNIT, 64, 14, 7, false); \
+        return wg_route(S_ <= 32 ? WG_ROUTE_WINDOW : WG_ROUTE_TILED, HD_, S_, NW_, false);                              \
+    }
+    WG_SAM_KERNELS(WG_SAM_ROUTE)
+#undef WG_SAM_ROUTE
+    return WG_ERR_UNSUPPORTED;
+}
+
+// Plain multi-head attention (optionally cross attention, optionally with an additive per-key bias).
+// Q rows: (b*q_rows_per_batch + i), head h at columns [h*hd, (h+1)*hd); same for K, V, O.
+extern "C" int wg_mha_bf16(const void* Q, long ldq, long q_rows_per_batch, const void* K, long ldk, const void* V, long ldv,
+                           long k_rows_per_batch, void* O, long ldo, long o_rows_per_batch, const float* key_bias,
+                           int B, int heads, int head_dim, int Lq, int Lk, float scale, void* stream) {
+    WG_REQUIRE(Q && K && V && O, "mha: null operand");
+    WG_REQUIRE(B > 0 && heads > 0 && Lq > 0 && Lk > 0, "mha: bad shape");
+    WG_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0, "mha: leading dimensions must be multiples of 8");
+    WG_REQUIRE((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V) & 15) == 0 && ((uintptr_t)O & 7) == 0, "mha: misaligned operand");
+    AttnArgs a{};
+    a.Q = (const bf16*)Q; a.K = (const bf16*)K; a.V = (const bf16*)V; a.O = (bf16*)O;
+    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
+    a.q_bs = q_rows_per_batch; a.k_bs = k_rows_per_batch; a.o_bs = o_rows_per_batch;
+    a.key_bias = key_bias; a.B = B; a.heads = heads; a.Lq = Lq; a.Lk = Lk; a.scale = scale;
+    hipStream_t st = (hipStream_t)stream;
+    const int groups = B * heads;
+    const int route = wg_mha_route_of(a, head_dim);
+    if (route < 0) {
+        wg_set_error("mha: head_dim %d with %d query blocks not supported (32, 64, 128; 16 for <= 32 queries)", head_dim, (Lq + 31) / 32);
+        return WG_ERR_UNSUPPORTED;
+    }
+    const int nw = wg_route_nw(route);
+    a.qchunks = ((Lq + 31) / 32 + nw - 1) / nw;
+    if (wg_route_family(route) == WG_ROUTE_PIPE) return wg_attn_pipe_launch(a, 0, nw, st);   // head_dim 64, no key bias, whole tiles: the pipelined loop
+#define WG_MHA_CASE(HD_, NW_) if (head_dim == HD_ && nw == NW_) return launch_attn<HD_, 0, NW_>(a, groups, st);
+    WG_MHA_KERNELS(WG_MHA_CASE)
+#undef WG_MHA_CASE
+    wg_set_error("mha: route %d has no launcher", route);
+    return WG_ERR_UNSUPPORTED;
+}
+
+extern "C" int wg_mha_route(int head_dim, int Lq, int Lk, int has_key_bias) {
+    if (head_dim <= 0 || Lq <= 0 || Lk <= 0) return WG_ERR_BAD_ARG;
+    static const float some_bias = 0.f;
+    AttnArgs a{};
+    a.Lq = Lq; a.Lk = Lk; a.key_bias = has_key_bias ? &some_bias : nullptr;
+    return wg_mha_route_of(a, head_dim);
 }
 
 // SAM ViT attention over a packed qkv buffer [B*Hg*Hg, 3*D] (q | k | v, heads contiguous inside each third).
@@ -976,17 +1040,21 @@ extern "C" int wg_sam_attn_relpos_bf16(const void* qkv, const void* qkv_bias, co
     return wg_sam_attn_impl(qkv, qkv_bias, rel_pos_h, rel_pos_w, out, nullptr, nullptr, 0, B, grid, window, heads, head_dim, scale, stream);
 }
 
+extern "C" int wg_sam_attn_route(int B, int grid, int window, int heads, int head_dim) {
+    if (B <= 0 || grid <= 0 || window <= 0 || window > grid || heads <= 0 || head_dim <= 0) return WG_ERR_BAD_ARG;
+    AttnArgs a{};
+    a.B = B; a.heads = heads; a.Hg = grid; a.nW = (grid + window - 1) / window; a.ldo = (long)heads * head_dim;
+    return wg_sam_route_of(a, head_dim, window);
+}
+
 // The fp8 chain's form (config C5's nn.Linear chain, ViT-B / ViT-L geometry): the attention output leaves as the proj GEMM's MX operand -- e4m3 bytes
 // out_q [B * grid^2, D] and E8M0 block scales out_mx [D / 32][mx_pitch] in wg_quantize_mx_fp8's group-128 layout, bit for bit what that pass makes of
 // the bf16 output -- and the bf16 tensor is never written.  head_dim 64 only (a 32-column block must not straddle two heads: not ViT-H's 80), on the
 // kernels that carry the epilogue (wg_sam_attn_mx_supported).
 extern "C" int wg_sam_attn_mx_supported(int B, int grid, int window, int heads, int head_dim) {
-    if (head_dim != 64 || B <= 0 || heads <= 0) return 0;
-    AttnArgs a{};
-    a.B = B; a.heads = heads; a.Hg = grid; a.nW = (grid + window - 1) / window; a.ldo = (long)heads * head_dim;
-    if (window == 64) return wg_attn_pipe_takes(a, head_dim, 64, 8) ? 1 : 0;
-    if (window == 14) return wg_attn_window_unit_takes(a) ? 1 : 0;
-    return 0;
+    if (head_dim != 64) return 0;
+    const int route = wg_sam_attn_route(B, grid, window, heads, head_dim);
+    return route > 0 && (wg_route_family(route) == WG_ROUTE_PIPE || wg_route_family(route) == WG_ROUTE_WINDOW_UNIT) ? 1 : 0;
 }
 extern "C" int wg_sam_attn_relpos_mx_bf16(const void* qkv, const void* qkv_bias, const void* rel_pos_h, const void* rel_pos_w, void* out_q, void* out_mx, long mx_pitch,
                                           int B, int grid, int window, int heads, int head_dim, float scale, void* stream) {
@@ -1013,22 +1081,20 @@ static int wg_sam_attn_impl(const void* qkv, const void* qkv_bias, const void* r
     hipStream_t st = (hipStream_t)stream;
     const int groups = B * a.nW * a.nW * heads;
     const int qblocks = (window * window + 31) / 32;
-#define WG_SAM_CASE(HD_, S_, NW_)                                  \
-    if (head_dim == HD_ && window == S_) {                         \
-        a.qchunks = (qblocks + NW_ - 1) / NW_;                     \
-        if (S_ == 64 && wg_attn_pipe_takes(a, head_dim, S_, NW_)) return wg_attn_pipe_launch(a, S_, NW_, st);                      \
-        if (HD_ == 64 && S_ == 14 && wg_attn_window_unit_takes(a)) return wg_attn_window_unit_launch(a, groups, st);      \
-        if constexpr (S_ <= 32) return launch_attn_window<HD_, S_, NW_>(a, groups, st);   \
-        else return launch_attn<HD_, S_, NW_>(a, groups, st);      \
-    }
-    WG_SAM_CASE(64, 14, 4)   // two 4-wave workgroups per window (one idle query slot in eight) measured 5 % faster than one of 7 waves
-    WG_SAM_CASE(64, 64, 8)
-    WG_SAM_CASE(64, 32, 8)
-    WG_SAM_CASE(32, 14, 7)
-    WG_SAM_CASE(32, 28, 5)
-    WG_SAM_CASE(80, 14, 7)   // (two 4-wave workgroups per window: 166.8 vs 160.6 us at B = 8, 16 heads)
-    WG_SAM_CASE(80, 64, 8)
+    const int route = wg_sam_route_of(a, head_dim, window);
+    if (route > 0) {
+        const int nw = wg_route_nw(route);
+        a.qchunks = (qblocks + nw - 1) / nw;
+        if (wg_route_family(route) == WG_ROUTE_PIPE) return wg_attn_pipe_launch(a, 64, nw, st);
+        if (wg_route_family(route) == WG_ROUTE_WINDOW_UNIT) return wg_attn_window_unit_launch(a, groups, st);
+#define WG_SAM_CASE(HD_, S_, NW_)                                                         \
+        if (head_dim == HD_ && window == S_) {                                            \
+            if constexpr (S_ <= 32) return launch_attn_window<HD_, S_, NW_>(a, groups, st);   \
+            else return launch_attn<HD_, S_, NW_>(a, groups, st);                         \
+        }
+        WG_SAM_KERNELS(WG_SAM_CASE)
 #undef WG_SAM_CASE
+    }
     wg_set_error("sam_attn: (head_dim %d, window %d) has no compiled kernel", head_dim, window);
     return WG_ERR_UNSUPPORTED;
 }

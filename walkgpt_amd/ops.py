@@ -249,6 +249,37 @@ def _rows_per_batch(t):
     return B, L, ld, (t.stride(0) // ld if B > 1 else L)
 
 
+def _mha_takes_small(hd, Lq, Lk, has_key_bias, small):
+    """mha()'s choice between wg_mha_small_bf16 (one wave per query) and wg_mha_bf16 (the tiled MFMA kernels)."""
+    if small is None:
+        small = hd < 32 or Lq <= 32 or Lk <= 32
+    if small and not has_key_bias and Lq <= 32 and Lk >= 256 and hd in (16, 32, 64, 128):
+        small = False  # few queries, many keys: one MFMA wave per (batch, head) reads K/V once for all queries
+    return small
+
+
+ROUTE_TILED, ROUTE_WINDOW, ROUTE_WINDOW_UNIT, ROUTE_PIPE, ROUTE_SMALL = 1, 2, 3, 4, 5
+
+
+def route_code(family, hd, S=0, waves=1, key_bias=0):
+    """The route codes of wg_mha_route / wg_sam_attn_route (include/walkgpt_hip.h); family ROUTE_SMALL (wg_mha_small_bf16, attn_small.hip:
+    one wave per query, or one lane per query where few keys meet many queries) exists at this level only."""
+    return family * 10000000 + hd * 10000 + S * 100 + waves * 10 + int(key_bias)
+
+
+def mha_route(hd, Lq, Lk, has_key_bias=False, small=None):
+    """Which kernel mha() would run for these shapes (under the current wg_attn_pipe_mode), as a route code; negative: none is compiled.
+    Host arithmetic, needs no GPU."""
+    if _mha_takes_small(hd, Lq, Lk, has_key_bias, small):
+        return route_code(ROUTE_SMALL, hd) if hd in (16, 32, 64, 128) and not has_key_bias else -2
+    return _lib.lib().wg_mha_route(hd, Lq, Lk, 1 if has_key_bias else 0)
+
+
+def sam_attention_route(B, grid, window, heads, hd):
+    """Which kernel sam_attention() would run (bf16 output), as a route code; negative: none is compiled."""
+    return _lib.lib().wg_sam_attn_route(B, grid, window, heads, hd)
+
+
 def mha(q, k, v, heads, scale, key_bias=None, out=None, small=None):
     """softmax(scale * q k^T + key_bias) v per head.  q [B,Lq,D], k/v [B,Lk,D] (bf16, may be column slices of a
     packed buffer); key_bias [B,Lk] fp32 additive or None.  `small` forces / forbids the one-wave-per-query kernel."""
@@ -263,11 +294,7 @@ def mha(q, k, v, heads, scale, key_bias=None, out=None, small=None):
     if out is None:
         out = torch.empty(B, Lq, D, device=q.device, dtype=_BF16)
     _, _, ldo, obs = _rows_per_batch(out)
-    if small is None:
-        small = hd < 32 or Lq <= 32 or Lk <= 32
-    if small and key_bias is None and Lq <= 32 and Lk >= 256 and hd in (16, 32, 64, 128):
-        small = False  # few queries, many keys: one MFMA wave per (batch, head) reads K/V once for all queries
-    if small:
+    if _mha_takes_small(hd, Lq, Lk, key_bias is not None, small):
         assert key_bias is None
         rc = _lib.lib().wg_mha_small_bf16(q.data_ptr(), ldq, qbs, k.data_ptr(), ldk, v.data_ptr(), ldv, kbs,
                                           out.data_ptr(), ldo, obs, B, heads, hd, Lq, Lk, float(scale), _stream())
