@@ -34,6 +34,8 @@ extern "C" {
 
 int wg_version(void);               /* major*10000 + minor*100 + patch; 300 = 0.3.0: adds wg_prompt_sparse_f32, wg_mask_embed_bf16 and
                                      * wg_normalize_pad_bf16 (SAM's point / box / mask prompts, Sam.preprocess); no existing argument list changed.
+                                     * Still 300 with the wg_amg_* and wg_nms_* entry points below (SamAutomaticMaskGenerator): they only add symbols, no
+                                     * existing argument list changed, and a caller finds them by symbol lookup, not by the version number.
                                      * 201 = 0.2.1: same entry points and argument lists as 0.2.0 (which changed them against 0.1.0: INTEGRATION.md
                                      * section 3); 0.2.1 = round 6's kernels (GELU form of the bf16 epilogues, above) */
 const char* wg_last_error(void);    /* thread-local, valid until the next failing call on this thread */
@@ -295,6 +297,40 @@ int wg_postprocess_masks_score_fused_f32(const float* low_res, float* out, float
 long wg_mask_score_workspace_floats(int N, long hw);
 int wg_mask_score_f32(const float* masks, float* score, float* workspace, long workspace_floats, int N, long hw,
                       void* stream);
+
+/* ---- SamAutomaticMaskGenerator behind the decoder (automatic_mask_generator.py:260-321, utils/amg.py) ----
+ * wg_amg_mask_stats_f32: Sam.postprocess_masks, the three thresholds of the stability score and the binary mask, the mask's box and its
+ *   bit-packing in one pass over the low-res logits [N, low_h, low_w] fp32; geometry arguments as wg_postprocess_masks_f32, and every pixel is
+ *   the very float that function writes (one shared copy of the arithmetic).  Nothing of full resolution is written but the bits.
+ *     stats int32 [N, 8] = {count(x > thr + off), count(x > thr - off), count(x > thr), x_min, y_min, x_max, y_max, 0}; the box is that of
+ *       x > thr in inclusive pixel indices, 0, 0, 0, 0 for an empty mask (batched_mask_to_box, amg.py:303-346).
+ *     bits uint32 [N, ceil(out_h / 32), out_w]: bit r of word (yb, x) = (pixel (32 yb + r, x) > thr); rows past out_h are 0; x varies fastest.
+ *     workspace: wg_amg_mask_stats_workspace_ints(N, out_h, out_w) int32 (8 per workgroup of 256 columns x 32 rows), written with plain
+ *       stores and folded by a second kernel in a fixed order: no atomics, the same bits every run.
+ *   Limits per call: N <= 65535, out_h * out_w < 2^31. */
+long wg_amg_mask_stats_workspace_ints(int N, int out_h, int out_w);
+int wg_amg_mask_stats_f32(const float* low_res, int* stats, unsigned* bits, int* workspace, long workspace_ints, int N, int low_h, int low_w,
+                          int img_size, int in_h, int in_w, int out_h, int out_w, float mask_threshold, float stability_offset, void* stream);
+/* wg_amg_rle_count_i32 / wg_amg_rle_write_i32: the change positions of mask_to_rle_pytorch (amg.py:107-135) applied to uncrop_masks
+ *   (amg.py:255-264) for the masks keep[0 .. K-1] (device int32 indices into the N bit planes `bits` of wg_amg_mask_stats_f32).  Mask k occupies
+ *   rows y0 .. y0 + out_h - 1 and columns x0 .. x0 + out_w - 1 of an H x W frame that is zero elsewhere; its change positions are every p in
+ *   1 .. H W - 1 with bit[p] != bit[p - 1] in the column-major flattening p = x H + y.
+ *     count: counts int32 [K, out_w] = positions that column x of mask k contributes.
+ *     write: offsets int64 [K * out_w] = the INCLUSIVE running sum of `counts` (the caller's one scan), total = its last element; positions
+ *       int32 [total], sorted per mask (the order is k, x, y); first int32 [K] = the frame's bit 0 (a set bit 0 means the code starts with a 0 run).
+ *   Limits: H * W < 2^31, K <= 65535.  A keep[k] outside [0, N) is clamped to a valid plane (it never becomes an address); the result for that
+ *   k is then another mask's code, so callers validate their lists (walkgpt_amd.ops.amg_rle does). */
+int wg_amg_rle_count_i32(const unsigned* bits, const int* keep, int* counts, int N, int K, int out_h, int out_w, int x0, int y0, int H, int W, void* stream);
+int wg_amg_rle_write_i32(const unsigned* bits, const int* keep, const long* offsets, int* positions, long total, int* first, int N, int K, int out_h,
+                         int out_w, int x0, int y0, int H, int W, void* stream);
+/* wg_nms_f32: greedy box NMS of one category (torchvision.ops.nms as automatic_mask_generator.py:206-211, :245-250 call it).  boxes [N, 4] fp32
+ *   XYXY (16-byte aligned), order int32 [N] = box indices by descending score (ties: the caller's stable sort decides).  A box suppresses a
+ *   later one when inter / (area_i + area_j - inter) > iou_threshold: area (x2 - x1)(y2 - y1), the intersection's extents clamped at 0, every
+ *   operation rounded once, the division correctly rounded.  keep int32 [N]: the kept indices in `order`'s order, n_keep int32 [1] their number.
+ *   workspace: wg_nms_workspace_words(N) 64-bit words (the suppression matrix [N, ceil(N / 64)]).  Limit: N <= 8192 (an 8 MB matrix).  order[] values outside [0, N) are clamped likewise. */
+long wg_nms_workspace_words(int N);
+int wg_nms_f32(const float* boxes, const int* order, float iou_threshold, int* keep, int* n_keep, unsigned long long* workspace, long workspace_words,
+               int N, void* stream);
 
 /* SURVEY.md 8(f) rows 1-2.  Per-mask one-pass statistics of fp32 logits [N, hw] against fp32 ground truth [N, hw]; scratch =
  * wg_mask_stats_workspace_floats(N, hw) floats.

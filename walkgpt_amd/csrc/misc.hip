@@ -2,6 +2,7 @@
 // 3x3 im2row, broadcast adds, layout transposes, the dense positional encoding, the hyper-network mask product,
 // the fused double-bilinear mask post-processing and the mask score.
 #include "wg_common.h"
+#include "post_common.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // Patch gather ("im2row" of a stride == kernel conv): images NCHW bf16 -> rows [B*gh*gw, Kpad], column order
@@ -261,30 +262,7 @@ extern "C" int wg_hyper_mask_dot(const void* up, const void* hyper, float* masks
 // source-index rule is reproduced exactly: src = max(scale*(dst+0.5)-0.5, 0), i0 = floor, i1 = i0 + (i0 < in-1).
 // Algorithmic bytes: read N*lh*lw*4, write N*out_h*out_w*4.
 // ------------------------------------------------------------------------------------------------------------
-// The four source-index scales of the two resamples (torch: input size / output size in fp32), divided on the host: a device-side `/` under
-// -ffast-math is a reciprocal approximation times the numerator.  (Through double: a ratio of two small integers is never a rounding tie.)
-struct PostScales { float s1y, s1x, s2y, s2x; };
-static PostScales wg_post_scales(int lh, int lw, int img, int in_h, int in_w, int out_h, int out_w) {
-    return PostScales{(float)((double)lh / (double)img), (float)((double)lw / (double)img), (float)((double)in_h / (double)out_h),
-                      (float)((double)in_w / (double)out_w)};
-}
-
-// One IEEE operation, one rounding, whatever the translation unit's floating-point mode: HIP's __fmul_rn / __fadd_rn are plain `*` / `+` unless
-// OCML_BASIC_ROUNDED_OPERATIONS is defined, and under -ffast-math the back end fuses and re-associates them (differently from one
-// instantiation of a kernel to the next: the fused-score form of the postprocess kernel differed from the plain one by an ulp in column 0).
-__device__ __forceinline__ float wg_mul_rn(float a, float b) { float r; asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float wg_add_rn(float a, float b) { float r; asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float wg_sub_rn(float a, float b) { float r; asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ void wg_src_index(int dst, float scale, int in_size, int& i0, int& i1, float& l1) {
-    // separate roundings (no FMA contraction) so the source index and weight match PyTorch's CPU kernel bit for bit
-    float s = wg_sub_rn(wg_mul_rn(scale, (float)dst + 0.5f), 0.5f);
-    s = s < 0.f ? 0.f : s;
-    i0 = (int)s;
-    i0 = i0 < in_size - 1 ? i0 : in_size - 1;
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    l1 = wg_sub_rn(s, (float)i0);
-}
-
+// (the index rule and the 16-tap evaluation live in post_common.h, shared with amg.hip)
 // grid (output column blocks, output rows, masks): no 64-bit index division per pixel (the first version spent more on `i % out_w` than on
 // the sixteen taps); the four first-resample index sets a pixel needs (two rows, two columns) are formed once and shared by its four taps.
 // SCORE: the workgroup also leaves {sum of sigmoid(x) over x > 0, count of x > 0} of its 256 pixels in score_ws -- the first pass of the mask
@@ -302,15 +280,10 @@ __global__ __launch_bounds__(256) void wg_postprocess_kernel(const float* __rest
     const int ox = blockIdx.x * 256 + threadIdx.x, n = blockIdx.z;
     float s_ = 0.f, c_ = 0.f;     // (a pixel outside the row contributes nothing to the score)
     if (ox < out_w) {
-        const float s1y = sc.s1y, s1x = sc.s1x, s2y = sc.s2y, s2x = sc.s2x;
         const float* m = low + (long)n * lh * lw;
         // the column taps of this thread's output column are the same for every row the workgroup covers (ROWS of them: the fused score wants
         // few, fat workgroups -- its tickets are adds to ONE word per mask and serialise at ~13 ns each)
-        int x0, x1, xa[2][2];            // [second-resample tap][first-resample tap]
-        float lx, lxa[2];
-        wg_src_index(ox, s2x, in_w, x0, x1, lx);
-        wg_src_index(x0, s1x, lw, xa[0][0], xa[0][1], lxa[0]);
-        wg_src_index(x1, s1x, lw, xa[1][0], xa[1][1], lxa[1]);
+        const PostCol col = wg_post_col(ox, sc, in_w, lw);
         // rows in chunks of up to four: all 64 taps of a chunk are requested before the first is used (row by row, a store between two rows' loads
         // made every row its own memory round trip); rows past the image repeat the last one and are not stored
         constexpr int CH = ROWS < 4 ? ROWS : 4;
@@ -320,33 +293,12 @@ __global__ __launch_bounds__(256) void wg_postprocess_kernel(const float* __rest
 #pragma unroll
             for (int r = 0; r < CH; ++r) {
                 const int oy = blockIdx.y * ROWS + r0 + r;
-                int y0, y1, ya[2][2];
-                wg_src_index(oy < out_h ? oy : out_h - 1, s2y, in_h, y0, y1, ly[r]);
-                wg_src_index(y0, s1y, lh, ya[0][0], ya[0][1], lya[r][0]);
-                wg_src_index(y1, s1y, lh, ya[1][0], ya[1][1], lya[r][1]);
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) {
-                        tap[r][j][i][0] = m[ya[j][0] * lw + xa[i][0]]; tap[r][j][i][1] = m[ya[j][0] * lw + xa[i][1]];
-                        tap[r][j][i][2] = m[ya[j][1] * lw + xa[i][0]]; tap[r][j][i][3] = m[ya[j][1] * lw + xa[i][1]];
-                    }
+                wg_post_taps(m, oy < out_h ? oy : out_h - 1, sc, in_h, lh, lw, col, tap[r], ly[r], lya[r]);
             }
 #pragma unroll
             for (int r = 0; r < CH; ++r) {
                 const int oy = blockIdx.y * ROWS + r0 + r;
-                float up[2][2];              // the img^2 intermediate at (y0|y1, x0|x1), operation by operation as torch's first resample
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) {
-                        const float wy = wg_sub_rn(1.f, lya[r][j]), wx = wg_sub_rn(1.f, lxa[i]);
-                        up[j][i] = wg_add_rn(wg_mul_rn(wy, wg_add_rn(wg_mul_rn(wx, tap[r][j][i][0]), wg_mul_rn(lxa[i], tap[r][j][i][1]))),
-                                             wg_mul_rn(lya[r][j], wg_add_rn(wg_mul_rn(wx, tap[r][j][i][2]), wg_mul_rn(lxa[i], tap[r][j][i][3]))));
-                    }
-                const float vy = wg_sub_rn(1.f, ly[r]), vx = wg_sub_rn(1.f, lx);
-                const float res = wg_add_rn(wg_mul_rn(vy, wg_add_rn(wg_mul_rn(vx, up[0][0]), wg_mul_rn(lx, up[0][1]))),
-                                            wg_mul_rn(ly[r], wg_add_rn(wg_mul_rn(vx, up[1][0]), wg_mul_rn(lx, up[1][1]))));
+                const float res = wg_post_eval(tap[r], ly[r], lya[r], col);
                 if (oy < out_h) {
                     out[((long)n * out_h + oy) * out_w + ox] = res;
                     if (SCORE != 0 && res > 0.f) { s_ += 1.0f / (1.0f + __expf(-res)); c_ += 1.f; }

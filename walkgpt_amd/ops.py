@@ -1088,3 +1088,95 @@ def match_cost(pred_logits, targets, point_coords):
     _lib.check(_lib.lib().wg_match_cost_f32(pred_logits.data_ptr(), targets.data_ptr(), point_coords.data_ptr(), cost.data_ptr(),
                                             ws.data_ptr(), nws, P, T, H, W, NP, _stream()), "wg_match_cost_f32")
     return cost
+
+
+# ---- SamAutomaticMaskGenerator behind the decoder (csrc/amg.hip) ---------------------------------------------------------------------------
+def amg_mask_stats(low_res, img_size, input_size, original_size, thr, offset):
+    """Low-res logits fp32 [N, lh, lw] -> (stats int32 [N, 8], bits int32 [N, ceil(H0 / 32), W0]) of the masks Sam.postprocess_masks would give,
+    without writing them (wg_amg_mask_stats_f32): stats = {count(x > thr + offset), count(x > thr - offset), count(x > thr), x_min, y_min, x_max,
+    y_max, 0}, the box as batched_mask_to_box (amg.py:303-346); bit r of bits[n, yb, x] = (pixel (32 yb + r, x) > thr).  (The words are the
+    kernel's uint32 in an int32 tensor: torch has no arithmetic on uint32.)"""
+    _need_gpu(low_res)
+    assert low_res.dtype == torch.float32 and low_res.is_contiguous() and low_res.dim() == 3
+    N, lh, lw = low_res.shape
+    H0, W0 = int(original_size[0]), int(original_size[1])
+    stats = torch.empty(N, 8, device=low_res.device, dtype=torch.int32)
+    bits = torch.empty(N, (H0 + 31) // 32, W0, device=low_res.device, dtype=torch.int32)
+    L = _lib.lib()
+    nws = L.wg_amg_mask_stats_workspace_ints(N, H0, W0)
+    ws = torch.empty(nws, device=low_res.device, dtype=torch.int32)
+    rc = L.wg_amg_mask_stats_f32(low_res.data_ptr(), stats.data_ptr(), bits.data_ptr(), ws.data_ptr(), nws, N, lh, lw, int(img_size),
+                                 int(input_size[0]), int(input_size[1]), H0, W0, float(thr), float(offset), _stream())
+    _lib.check(rc, "wg_amg_mask_stats_f32")
+    return stats, bits
+
+
+def rle_from_positions(positions, ends, first, size):
+    """The host half of amg_rle: sorted change positions of all masks (one int array), `ends` = where each mask's run of them stops, first[k] =
+    the mask's bit 0 -> the uncompressed RLEs of mask_to_rle_pytorch (amg.py:120-135): the runs are the differences of [0, positions.., H W],
+    with a leading 0 when the mask starts set.  numpy only; one np.diff per mask, no loop over runs or pixels."""
+    import numpy as np
+    H, W = int(size[0]), int(size[1])
+    out, start = [], 0
+    for k, end in enumerate(np.asarray(ends).tolist()):
+        edges = np.empty(end - start + 2, dtype=np.int64)
+        edges[0], edges[-1] = 0, H * W
+        edges[1:-1] = positions[start:end]
+        runs = np.diff(edges).tolist()
+        out.append({"size": [H, W], "counts": ([0] + runs) if first[k] else runs})
+        start = end
+    return out
+
+
+def amg_rle(bits, keep, crop_box, frame_size):
+    """Uncompressed RLEs (mask_to_rle_pytorch of uncrop_masks, amg.py:107-135, :255-264) of the bit planes bits[keep[k]] (amg_mask_stats's layout),
+    each placed at crop_box = [x0, y0, x1, y1] of an (H, W) frame: a list of {"size": [H, W], "counts": [...]}.  `keep`: int32 / int64 indices
+    on the device, every one in [0, N) (checked).  Count pass, one scan (torch.cumsum), one blocking read of its total (with the range check of
+    `keep`) before the write pass, then the blocking copies of the positions, the per-mask totals and the first bits to the host."""
+    _need_gpu(bits, keep)
+    assert bits.dtype == torch.int32 and bits.is_contiguous() and bits.dim() == 3
+    assert keep.dim() == 1 and keep.dtype in (torch.int32, torch.int64)
+    H, W = int(frame_size[0]), int(frame_size[1])
+    x0, y0, x1, y1 = (int(v) for v in crop_box)
+    N, hb, out_w = bits.shape
+    out_h = y1 - y0
+    assert out_w == x1 - x0 and hb == (out_h + 31) // 32, "bits %s do not belong to crop box %s" % (tuple(bits.shape), list(crop_box))
+    K = keep.shape[0]
+    if K == 0:
+        return []
+    keep = keep.to(torch.int32).contiguous()
+    L = _lib.lib()
+    counts = torch.empty(K, out_w, device=bits.device, dtype=torch.int32)
+    _lib.check(L.wg_amg_rle_count_i32(bits.data_ptr(), keep.data_ptr(), counts.data_ptr(), N, K, out_h, out_w, x0, y0, H, W, _stream()),
+               "wg_amg_rle_count_i32")
+    offsets = torch.cumsum(counts.reshape(-1), 0, dtype=torch.int64)
+    # (the kernels clamp an index outside the planes instead of reading there; the list is judged with the read of the total)
+    total, bad = torch.stack([offsets[-1], ((keep < 0) | (keep >= N)).sum()]).tolist()
+    if bad:
+        raise _lib.WalkgptHipError("amg_rle: %d of the %d indices in `keep` lie outside the %d bit planes" % (bad, K, N))
+    positions = torch.empty(max(total, 1), device=bits.device, dtype=torch.int32)
+    first = torch.empty(K, device=bits.device, dtype=torch.int32)
+    _lib.check(L.wg_amg_rle_write_i32(bits.data_ptr(), keep.data_ptr(), offsets.data_ptr(), positions.data_ptr(), total, first.data_ptr(), N, K,
+                                      out_h, out_w, x0, y0, H, W, _stream()), "wg_amg_rle_write_i32")
+    ends = offsets.reshape(K, out_w)[:, -1]
+    return rle_from_positions(positions[:total].cpu().numpy(), ends.cpu().numpy(), first.cpu().numpy(), (H, W))
+
+
+def nms(boxes, scores, iou_threshold):
+    """torchvision.ops.nms (one category, which is how automatic_mask_generator.py calls batched_nms): boxes [N, 4] XYXY, scores [N] -> int64
+    indices of the kept boxes by descending score (wg_nms_f32).  The order is a stable descending sort: equal scores keep their input order."""
+    _need_gpu(boxes, scores)
+    assert boxes.dim() == 2 and boxes.shape[1] == 4 and scores.shape == (boxes.shape[0],)
+    N = boxes.shape[0]
+    if N == 0:
+        return torch.empty(0, device=boxes.device, dtype=torch.int64)
+    boxes = boxes.float().contiguous()
+    order = torch.sort(scores, descending=True, stable=True)[1].to(torch.int32)
+    keep = torch.empty(N, device=boxes.device, dtype=torch.int32)
+    n_keep = torch.empty(1, device=boxes.device, dtype=torch.int32)
+    L = _lib.lib()
+    nws = L.wg_nms_workspace_words(N)
+    ws = torch.empty(nws, device=boxes.device, dtype=torch.int64)
+    _lib.check(L.wg_nms_f32(boxes.data_ptr(), order.data_ptr(), float(iou_threshold), keep.data_ptr(), n_keep.data_ptr(), ws.data_ptr(), nws, N,
+                            _stream()), "wg_nms_f32")
+    return keep[:int(n_keep.item())].to(torch.int64)

@@ -75,16 +75,21 @@ class SamPredictor:
         """Batched prompts already in the input frame (BxNx2, BxN, Bx4, Bx1x256x256) -> (masks BxCxHxW, iou BxC, low-res logits BxCx256x256)."""
         if not self.is_image_set:
             raise RuntimeError("An image must be set with .set_image(...) before mask prediction.")
-        points = (point_coords, point_labels) if point_coords is not None else None
-        pe = self.model.prompt_encoder
-        sparse, dense = pe(points=points, boxes=boxes, masks=mask_input)
-        low_res_masks, iou_predictions = self.model.mask_decoder(image_embeddings=self.features, image_pe=pe.get_dense_pe(),
-                                                                 sparse_prompt_embeddings=sparse, dense_prompt_embeddings=dense,
-                                                                 multimask_output=multimask_output)
+        low_res_masks, iou_predictions = self._predict_low_res(point_coords, point_labels, boxes, mask_input, multimask_output)
         masks = self.model.postprocess_masks(low_res_masks, self.input_size, self.original_size)
         if not return_logits:
             masks = masks > self.model.mask_threshold
         return masks, iou_predictions, low_res_masks
+
+    @torch.no_grad()
+    def _predict_low_res(self, point_coords, point_labels, boxes, mask_input, multimask_output):
+        """predict_torch up to the decoder: (low-res logits BxCx256x256, iou BxC), nothing at the frame's size (SamAutomaticMaskGenerator
+        takes its statistics straight from the low-res logits)."""
+        points = (point_coords, point_labels) if point_coords is not None else None
+        pe = self.model.prompt_encoder
+        sparse, dense = pe(points=points, boxes=boxes, masks=mask_input)
+        return self.model.mask_decoder(image_embeddings=self.features, image_pe=pe.get_dense_pe(), sparse_prompt_embeddings=sparse,
+                                       dense_prompt_embeddings=dense, multimask_output=multimask_output)
 
     def get_image_embedding(self) -> torch.Tensor:
         """The current image's embedding, 1xCxHxW."""
