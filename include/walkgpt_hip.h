@@ -528,6 +528,44 @@ int wg_nce_tail_bwd_dev_f32(const void* z, const void* vp, const float* sim, con
 int wg_nce_tail_bwd_f32(const void* z, const void* vp, const float* sim, const int* own_row, const float* lse_m, float g, void* dz, void* dvp,
                         float* dsim, int M, int rows, int N, int D, float temperature, int exclude_same_row, void* stream);
 
+/* ---- the LLaMA generate path (csrc/llama.hip; host: walkgpt_amd/llama_hip.py).  head_dim 128, bf16 data, fp32 arithmetic, fixed summation
+ * order.  KV cache: K and V [rows, cap, H] bf16 per layer (H = heads * 128, cap % 64 == 0); key mask uint8 [rows, cap], 1 = attend.
+ * Device state int32: past_len -- for rope_cache / attn_prefill the number of tokens already cached (token j of the call sits at position
+ * past_len + j), for attn_decode / pick_token the position of the current token; every index derived from it is clamped inside the kernels.
+ *
+ * wg_rmsnorm_rows_bf16: y = x * rsqrt(mean(x^2) + eps) * w per row, D % 8 == 0.  slot != NULL: row r goes to
+ *   y + r * y_batch_stride + clamp(*slot + slot_add, 0, slot_cap - 1) * ldy instead of y + r * ldy. */
+int wg_rmsnorm_rows_bf16(const void* x, long ldx, const void* w, void* y, long ldy, int M, int D, float eps, const int* slot, int slot_add,
+                         int slot_cap, long y_batch_stride, void* stream);
+/* wg_llama_rope_cache_bf16: rows [rows * L, 3H] of q | k | v; q and k rotated with the rotate_half pairing (i, i + 64) at position
+ *   *past_len + j from fp32 tables cos, sin [max_pos, 64]; q -> q_out [rows * L, H], k and v -> their cache slots (a position outside
+ *   [0, cap) writes no slot). */
+int wg_llama_rope_cache_bf16(const void* qkv, long ldqkv, const float* cos_table, const float* sin_table, int max_pos, const int* past_len,
+                             void* q_out, long ldq, void* k_cache, void* v_cache, int rows, int L, int heads, int cap, void* stream);
+/* wg_llama_attn_prefill_bf16: causal attention of L queries per row (query j at position *past_len + j) over the cached keys 0 .. position
+ *   whose mask byte is set; q, out [rows * L, H]; L <= cap; the mask 4-byte aligned. */
+int wg_llama_attn_prefill_bf16(const void* q, long ldq, const void* k_cache, const void* v_cache, const unsigned char* mask, void* out, long ldo,
+                               const int* past_len, int rows, int L, int heads, int cap, float scale, void* stream);
+/* wg_llama_attn_decode_bf16: one query per (row, head) over keys 0 .. *past_len with the key mask; a fixed number of key splits per
+ *   (row, head), combined in index order by a second launch.  workspace: wg_llama_attn_decode_workspace_floats(rows, heads) floats. */
+long wg_llama_attn_decode_workspace_floats(int rows, int heads);
+int wg_llama_attn_decode_bf16(const void* q, long ldq, const void* k_cache, const void* v_cache, const unsigned char* mask, float* workspace,
+                              long workspace_floats, void* out, long ldo, const int* past_len, int rows, int heads, int cap, float scale,
+                              void* stream);
+/* wg_llama_gemv_bf16: out[m][n] = sum_k xh[m][k] W[n][k], M <= 8, K % 128 == 0, weights (contiguous [N_i, K], read once) in up to three
+ *   segments that form the column ranges of one output; any N_i >= 1.  gamma != NULL: xh = x * rstd(row) * gamma (RMSNorm, eps), else xh = x.
+ *   residual != NULL: out = residual + product (residual may be out).  pair: out[n] = silu(W_0[n] . xh) * (W_1[n] . xh), N_0 == N_1.
+ *   out_f32: fp32 output. */
+int wg_llama_gemv_bf16(const void* x, long ldx, const void* w0, int n0, const void* w1, int n1, const void* w2, int n2, int K, const void* gamma,
+                       float eps, const void* residual, long ldr, void* out, long ldo, int out_f32, int pair, int M, void* stream);
+/* wg_llama_silu_mul_bf16: out[m][i] = silu(gate_up[m][i]) * gate_up[m][I + i], I % 8 == 0 */
+int wg_llama_silu_mul_bf16(const void* gate_up, long ldgu, void* out, long ldo, int M, int I, void* stream);
+/* wg_llama_pick_token: per row (rows <= 8) the argmax of fp32 logits [rows, V] (lowest index on a tie); a finished row emits pad and
+ *   finished |= (token == eos) (eos < 0: neither); tokens[row][n_new] = token (int64 [rows, tok_cap]); embed[token] -> x_next[row];
+ *   mask[row][past_len + 1] = 1; state = {past_len, n_new} both move on by one, past_len not beyond cap - 1, n_new not beyond tok_cap. */
+int wg_llama_pick_token(const float* logits, long ldl, const void* embed, int n_embed, void* x_next, long ldx, long long* tokens, int tok_cap,
+                        int* finished, unsigned char* mask, int* state, int eos, int pad, int rows, int V, int H, int cap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

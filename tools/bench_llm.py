@@ -1,0 +1,103 @@
+"""Greedy generation of the language model: the stock path (`walkgptForCausalLM._generate` with the switch off: one transformers forward per
+token) against the HIP LLaMA path (walkgpt_amd/llama_hip.py), eager and graphed, in one process on one GPU.
+
+Default shape: a random-init bf16 LLaMA-7B (32 layers, 4096 hidden, 11008 intermediate, 32 heads; 13.5 GB), rows 1, L0 = 320 (64 text + 256 image
+positions), 128 new tokens, no eos.  Per path the median of `--runs` runs of: the prefill alone, the whole generation, and from the two the decode
+time per token, (generation - prefill) / (new - 1).  Also: the weight bytes a decode step streams / its time, as a share of the 6.29 TB/s copy rate
+measured on an MI355X.  Prints one JSON line; results belong in profiles/llm_generate.md.
+
+    python tools/bench_llm.py [--layers 32] [--rows 1] [--l0 320] [--new 128] [--runs 5] [--one-step]
+--one-step: no timing; after a warm generation, replay ONE graphed decode step (for `rocprofv3 --kernel-trace --stats -- python tools/bench_llm.py
+--one-step`, whose per-kernel table then holds that step on top of the warm-up)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+from types import SimpleNamespace
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+COPY_RATE = 6.29e12      # bytes / s, the measured device-to-device copy rate of an MI355X
+
+
+def build(layers, dev):
+    from transformers import LlamaConfig, LlamaForCausalLM
+    cfg = LlamaConfig(vocab_size=32000, hidden_size=4096, intermediate_size=11008, num_hidden_layers=layers, num_attention_heads=32,
+                      num_key_value_heads=32, max_position_embeddings=2048)
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(torch.bfloat16)      # as causal_lm._build_language_model: a 7B random init in fp32 would need 27 GB
+    try:
+        with torch.device(dev):
+            llm = LlamaForCausalLM(cfg)
+    finally:
+        torch.set_default_dtype(prev)
+    return llm.eval()
+
+
+def timed(fn, runs):
+    out = []
+    for _ in range(runs):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--layers", type=int, default=32)
+    ap.add_argument("--rows", type=int, default=1)
+    ap.add_argument("--l0", type=int, default=320)
+    ap.add_argument("--new", type=int, default=128)
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--one-step", action="store_true")
+    a = ap.parse_args()
+    from walkgpt_amd.causal_lm import walkgptForCausalLM
+    from walkgpt_amd.llama_hip import LlamaHipRunner
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    llm = build(a.layers, dev)
+    g = torch.Generator().manual_seed(1)
+    emb = llm.get_input_embeddings().weight[torch.randint(0, 32000, (a.rows, a.l0), generator=g).to(dev)]
+    mask = torch.ones(a.rows, a.l0, dtype=torch.bool, device=dev)
+    runner = LlamaHipRunner(llm)
+    # _generate as the model runs it, without the grounding modules around it: `self` only has to carry what _generate reads
+    stock = SimpleNamespace(llm=llm, eos_token_id=None, config=SimpleNamespace(pad_token_id=None), _hip_llm=None)
+    with torch.no_grad():
+        if a.one_step:
+            runner.generate(emb, mask, 4)
+            torch.cuda.synchronize()
+            runner._graph[0].replay()
+            torch.cuda.synchronize()
+            return
+        paths = {
+            "stock": (lambda: llm(inputs_embeds=emb, attention_mask=mask, use_cache=True, output_hidden_states=True),
+                      lambda: walkgptForCausalLM._generate(stock, emb, mask, a.new)),
+            "hip_eager": (lambda: runner.prefill(emb, mask), lambda: runner.generate(emb, mask, a.new, graph=False)),
+            "hip_graph": (lambda: runner.prefill(emb, mask), lambda: runner.generate(emb, mask, a.new, graph=True)),
+        }
+        res = {"layers": a.layers, "rows": a.rows, "l0": a.l0, "new": a.new, "runs": a.runs}
+        tokens = {}
+        for name, (prefill, generate) in paths.items():
+            prefill()
+            tokens[name] = generate()[0]               # warm-up (and, for the graphed path, the capture)
+            p, t = timed(prefill, a.runs), timed(generate, a.runs)
+            res[name] = {"prefill_ms": round(p, 3), "generate_ms": round(t, 3), "decode_ms_per_token": round((t - p) / max(1, a.new - 1), 4)}
+        w = sum(t.numel() * 2 for lw in runner._layers() for t in lw if t.dim() == 2) + llm.lm_head.weight.numel() * 2
+        d = res["hip_graph"]["decode_ms_per_token"] * 1e-3
+        res["weight_bytes_per_token"] = w
+        res["hip_graph_share_of_copy_rate"] = round(w / d / COPY_RATE, 4)
+        res["hip_graph_vs_stock_decode"] = round(res["stock"]["decode_ms_per_token"] / res["hip_graph"]["decode_ms_per_token"], 3)
+        res["tokens_equal_eager_graph"] = bool(tokens["hip_eager"].equal(tokens["hip_graph"]))
+        res["tokens_agreeing_with_stock"] = round(float((tokens["hip_graph"] == tokens["stock"]).float().mean()), 3)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

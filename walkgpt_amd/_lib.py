@@ -136,6 +136,18 @@ SIGNATURES = {
     "wg_amg_rle_count_i32": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "wg_amg_rle_write_i32": [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "wg_nms_f32": [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p],
+    "wg_rmsnorm_rows_bf16": [c_void_p, c_long, c_void_p, c_void_p, c_long, c_int, c_int, c_float, c_void_p, c_int, c_int, c_long, c_void_p],
+    "wg_llama_rope_cache_bf16": [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_int, c_int, c_int,
+                                 c_int, c_void_p],
+    "wg_llama_attn_prefill_bf16": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_int, c_float,
+                                   c_void_p],
+    "wg_llama_attn_decode_bf16": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_long, c_void_p, c_int, c_int, c_int,
+                                  c_float, c_void_p],
+    "wg_llama_gemv_bf16": [c_void_p, c_long, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_float, c_void_p, c_long, c_void_p,
+                           c_long, c_int, c_int, c_int, c_void_p],
+    "wg_llama_silu_mul_bf16": [c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_void_p],
+    "wg_llama_pick_token": [c_void_p, c_long, c_void_p, c_int, c_void_p, c_long, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                            c_int, c_int, c_int, c_void_p],
 }
 _SPECIAL = {"wg_last_error": (ctypes.c_char_p, []), "wg_version": (c_int, []),
             "wg_mask_score_workspace_floats": (c_long, [c_int, c_long]),
@@ -144,6 +156,7 @@ _SPECIAL = {"wg_last_error": (ctypes.c_char_p, []), "wg_version": (c_int, []),
             "wg_match_cost_workspace_floats": (c_long, [c_int, c_int, c_int]),
             "wg_amg_mask_stats_workspace_ints": (c_long, [c_int, c_int, c_int]),
             "wg_nms_workspace_words": (c_long, [c_int]),
+            "wg_llama_attn_decode_workspace_floats": (c_long, [c_int, c_int]),
             "wg_gemm_bwd_splits": (c_int, [c_int, c_int, c_int]),
             "wg_gemm_bwd_workspace_floats": (c_long, [c_int, c_int, c_int, c_int]),
             "wg_layernorm_bwd_det_workspace_floats": (c_long, [c_int, c_int]),

@@ -495,6 +495,27 @@ class walkgptForCausalLM(nn.Module):  # noqa: N801  (the reference's class name)
                 "nce_loss": nce_loss, "mask_loss": mask_loss}
 
     # -- generation (walkgpt.py:629-639, evaluation_walkgpt.py:569-577) ---------------------------------------------------------------
+    _hip_llm = None           # the LlamaHipRunner while enable_hip_llm() is on; None (the default): the stock transformers path below
+
+    def enable_hip_llm(self, on: bool = True):
+        """Opt-in: `_generate` (so `generate` and `evaluate`) runs the language model through the HIP LLaMA path of llama_hip.py -- a GEMM
+        prefill and a graph-captured KV-cache decode step -- instead of one transformers forward per token.  Raises with
+        LlamaHipRunner.supports' reason when the model does not qualify (GQA, head_dim != 128, unmerged LoRA, ...).  model_forward and
+        training never go through it; `enable_hip_llm(False)` drops the runner and its cache."""
+        if not on:
+            self._hip_llm = None
+            return self
+        from .llama_hip import LlamaHipRunner
+        ok, why = LlamaHipRunner.supports(self.llm)
+        if not ok:
+            raise ValueError("enable_hip_llm: " + why)
+        self._hip_llm = LlamaHipRunner(self.llm)
+        return self
+
+    @property
+    def hip_llm_enabled(self):
+        return self._hip_llm is not None
+
     def _generate(self, embeds, attn, max_new_tokens):
         """Greedy decoding through the language model's KV cache.  The reference generates with `config.use_cache = False`
         (walkgpt.py:149), i.e. re-runs the whole sequence per new token, and reads `outputs.hidden_states[-1]` = the last step's
@@ -505,6 +526,8 @@ class walkgptForCausalLM(nn.Module):  # noqa: N801  (the reference's class name)
         eos = self.eos_token_id
         pad = getattr(self.config, "pad_token_id", None)
         pad = eos if pad is None else pad
+        if self._hip_llm is not None:
+            return self._hip_llm.generate(embeds, attn, max_new_tokens, eos=eos, pad=pad)
         out = self.llm(inputs_embeds=embeds, attention_mask=attn, use_cache=True, output_hidden_states=True)
         hs, new = [out.hidden_states[-1]], []
         finished = torch.zeros(embeds.shape[0], dtype=torch.bool, device=embeds.device)

@@ -1,0 +1,666 @@
+// The LLaMA generate path (walkgpt_amd/llama_hip.py): RMSNorm, RoPE + KV-cache write, causal prefill attention, split-key decode
+// attention, the decode GEMV and the device-side token pick.  bf16 data, fp32 arithmetic, no float atomics, every sum in a fixed
+// order (a run repeats bit for bit).  No launch function allocates or synchronises: all of them run inside a graph capture.
+//
+// Device state of a generation (int32, read by the kernels so that a captured decode step bakes in no length):
+//   past_len   prefill / rope_cache: the number of tokens already in the cache (token j of the call sits at position past_len + j);
+//              decode attention and the pick: the position of the CURRENT token -- its query sees keys 0 .. past_len.  The pick sets
+//              mask[row][past_len + 1] and increments it, so the next step's token lands on the next slot.
+//   n_new      how many tokens the pick has emitted.
+// Every index derived from that state is clamped to the cache capacity `cap` (or to the table it indexes) inside the kernel: a stale
+// or garbage state gives wrong numbers, never an access outside the buffers.
+//
+// Cache layout: K and V are [rows, cap, H] bf16 (H = heads * 128), position-major, one pair per layer; cap % 64 == 0.
+// Key mask: uint8 [rows, cap], 1 = attend, the same for every query of a row.
+#include "wg_common.h"
+
+#define WG_LLAMA_HD 128
+#define WG_LLAMA_SPLITS 8        // key splits of the decode attention (fixed: the combine order must not depend on the shape)
+#define WG_LLAMA_PART 132        // floats per decode partial: o[128], m, l, 2 pad (keeps rows 16-byte aligned)
+#define WG_NEG_BIG (-1.0e30f)
+
+__device__ __forceinline__ int wg_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__device__ __forceinline__ long wg_clampl(long v, long lo, long hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// ---- a. RMSNorm ---------------------------------------------------------------------------------------------------------------------
+// y = x * rsqrt(mean(x^2) + eps) * w, one rounding (to bf16) at the end.  One 256-thread block per row.
+// slot != null: row r is written to y + r * y_bs + clamp(*slot + slot_add, 0, slot_cap - 1) * ldy (the decode step's hidden-state slot).
+__global__ __launch_bounds__(256) void wg_rmsnorm_rows_kernel(const bf16* x, long ldx, const bf16* w, bf16* y, long ldy, int D, float eps,
+                                                              const int* slot, int slot_add, int slot_cap, long y_bs) {
+    __shared__ float red[4];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const bf16* xr = x + (long)row * ldx;
+    float ss = 0.f;
+    for (int k = tid * 8; k < D; k += 2048) {
+        const bf16x8 t = *(const bf16x8*)(xr + k);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) ss += (float)t[e] * (float)t[e];
+    }
+    ss = wg_wave_sum(ss);
+    if ((tid & 63) == 0) red[tid >> 6] = ss;
+    __syncthreads();
+    const float rstd = 1.0f / sqrtf(((red[0] + red[1]) + (red[2] + red[3])) / (float)D + eps);
+    bf16* yr = slot ? y + (long)row * y_bs + wg_clampl((long)*slot + slot_add, 0, slot_cap - 1) * ldy : y + (long)row * ldy;
+    for (int k = tid * 8; k < D; k += 2048) {
+        const bf16x8 t = *(const bf16x8*)(xr + k), g = *(const bf16x8*)(w + k);
+        bf16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (bf16)((float)t[e] * rstd * (float)g[e]);
+        *(bf16x8*)(yr + k) = o;
+    }
+}
+
+extern "C" int wg_rmsnorm_rows_bf16(const void* x, long ldx, const void* w, void* y, long ldy, int M, int D, float eps, const int* slot,
+                                    int slot_add, int slot_cap, long y_batch_stride, void* stream) {
+    WG_REQUIRE(x && w && y, "rmsnorm: null operand");
+    WG_REQUIRE(M > 0 && D > 0 && D % 8 == 0, "rmsnorm: bad shape (M %d, D %d; D must be a multiple of 8)", M, D);
+    WG_REQUIRE(ldx >= D && ldy >= D && ldx % 8 == 0 && ldy % 8 == 0, "rmsnorm: leading dimensions must be multiples of 8 and >= D");
+    WG_REQUIRE((((uintptr_t)x | (uintptr_t)w | (uintptr_t)y) & 15) == 0, "rmsnorm: misaligned operand");
+    WG_REQUIRE(!slot || (slot_cap > 0 && y_batch_stride >= (long)slot_cap * ldy), "rmsnorm: slot output needs slot_cap rows inside y_batch_stride");
+    hipLaunchKernelGGL(wg_rmsnorm_rows_kernel, dim3(M), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, ldx, (const bf16*)w, (bf16*)y, ldy, D, eps,
+                       slot, slot_add, slot_cap, y_batch_stride);
+    return wg_check_launch("wg_rmsnorm_rows_bf16");
+}
+
+// ---- b. RoPE + cache write ----------------------------------------------------------------------------------------------------------
+// One thread per (token, head, 8 of the 64 rotation pairs): pair (i, i + 64) as transformers' rotate_half,
+//   out[i] = x[i] cos[i] - x[i + 64] sin[i],   out[i + 64] = x[i + 64] cos[i] + x[i] sin[i]      (fp32, one rounding)
+// q -> q_out [rows L, H]; rotated k and plain v -> the cache slot of position past_len + j.  A position outside [0, cap) writes no cache
+// slot (and reads the table's last row).
+struct RopeArgs {
+    const bf16* qkv; long ldqkv;
+    const float* cos; const float* sin; int max_pos;
+    const int* past_len;
+    bf16* q_out; long ldq;
+    bf16* kc; bf16* vc;
+    int rows, L, heads, cap;
+};
+
+__device__ __forceinline__ void wg_rope8(const bf16x8 lo, const bf16x8 hi, const float* c, const float* s, bf16x8& olo, bf16x8& ohi) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float a = (float)lo[e], b = (float)hi[e];
+        olo[e] = (bf16)(a * c[e] - b * s[e]);
+        ohi[e] = (bf16)(b * c[e] + a * s[e]);
+    }
+}
+
+__global__ __launch_bounds__(256) void wg_llama_rope_cache_kernel(RopeArgs a) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const long total = (long)a.rows * a.L * a.heads * 8;
+    if (i >= total) return;
+    const int c8 = (int)(i & 7);
+    const int head = (int)((i >> 3) % a.heads);
+    const long tok = (i >> 3) / a.heads;            // row * L + j
+    const int j = (int)(tok % a.L), row = (int)(tok / a.L);
+    const int H = a.heads * WG_LLAMA_HD;
+    const long pos = (long)*a.past_len + j;
+    const int tp = (int)(pos < 0 ? 0 : (pos > a.max_pos - 1 ? a.max_pos - 1 : pos));
+    float c[8], s[8];
+    {
+        const f32x4* cp = (const f32x4*)(a.cos + (long)tp * 64 + c8 * 8);
+        const f32x4* sp = (const f32x4*)(a.sin + (long)tp * 64 + c8 * 8);
+        const f32x4 c0 = cp[0], c1 = cp[1], s0 = sp[0], s1 = sp[1];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { c[e] = c0[e]; c[4 + e] = c1[e]; s[e] = s0[e]; s[4 + e] = s1[e]; }
+    }
+    const bf16* src = a.qkv + tok * a.ldqkv + head * WG_LLAMA_HD + c8 * 8;
+    bf16x8 olo, ohi;
+    wg_rope8(*(const bf16x8*)src, *(const bf16x8*)(src + 64), c, s, olo, ohi);
+    bf16* qo = a.q_out + tok * a.ldq + head * WG_LLAMA_HD + c8 * 8;
+    *(bf16x8*)qo = olo;
+    *(bf16x8*)(qo + 64) = ohi;
+    if (pos < 0 || pos >= a.cap) return;
+    const long slot = ((long)row * a.cap + pos) * H + head * WG_LLAMA_HD + c8 * 8;
+    wg_rope8(*(const bf16x8*)(src + H), *(const bf16x8*)(src + H + 64), c, s, olo, ohi);
+    *(bf16x8*)(a.kc + slot) = olo;
+    *(bf16x8*)(a.kc + slot + 64) = ohi;
+    *(bf16x8*)(a.vc + slot) = *(const bf16x8*)(src + 2 * H);
+    *(bf16x8*)(a.vc + slot + 64) = *(const bf16x8*)(src + 2 * H + 64);
+}
+
+extern "C" int wg_llama_rope_cache_bf16(const void* qkv, long ldqkv, const float* cos_table, const float* sin_table, int max_pos,
+                                        const int* past_len, void* q_out, long ldq, void* k_cache, void* v_cache, int rows, int L, int heads,
+                                        int cap, void* stream) {
+    WG_REQUIRE(qkv && cos_table && sin_table && past_len && q_out && k_cache && v_cache, "llama_rope_cache: null operand");
+    WG_REQUIRE(rows > 0 && L > 0 && heads > 0 && max_pos > 0, "llama_rope_cache: bad shape");
+    WG_REQUIRE(cap > 0 && cap % 64 == 0, "llama_rope_cache: cache capacity %d must be a positive multiple of 64", cap);
+    const long H = (long)heads * WG_LLAMA_HD;
+    WG_REQUIRE(ldqkv >= 3 * H && ldq >= H && ldqkv % 8 == 0 && ldq % 8 == 0, "llama_rope_cache: leading dimensions too small or not multiples of 8");
+    WG_REQUIRE((((uintptr_t)qkv | (uintptr_t)cos_table | (uintptr_t)sin_table | (uintptr_t)q_out | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15) == 0,
+               "llama_rope_cache: misaligned operand");
+    RopeArgs a{(const bf16*)qkv, ldqkv, cos_table, sin_table, max_pos, past_len, (bf16*)q_out, ldq, (bf16*)k_cache, (bf16*)v_cache, rows, L, heads, cap};
+    const long total = (long)rows * L * heads * 8;
+    hipLaunchKernelGGL(wg_llama_rope_cache_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return wg_check_launch("wg_llama_rope_cache_bf16");
+}
+
+// ---- c. prefill attention -----------------------------------------------------------------------------------------------------------
+// Flash-style, one wave per (32 queries, head, row), 32 keys per step.  The score product is taken swapped, S^T = K Q^T
+// (mfma_f32_32x32x16_bf16, A = K rows and B = Q rows, both 16-byte loads straight from memory), so a lane holds 16 scores of ONE query
+// (column = lane & 31; the other 16 keys sit in lane ^ 32) and the running max / sum are per lane.  P is rounded to bf16 and is, as it
+// stands in the accumulator registers, the B operand of O^T = V^T P^T; the V^T fragments are gathered from a [32][128] LDS image of
+// the V tile.  The row sum is taken from the unrounded P.  Query j sits at position past + j and sees keys <= its position whose mask
+// byte is set.  V rows beyond the block's last visible key are staged as zeros (an unwritten cache slot may hold anything).
+struct PrefillArgs {
+    const bf16* q; long ldq;
+    const bf16* kc; const bf16* vc;
+    const unsigned char* mask;
+    bf16* out; long ldo;
+    const int* past_len;
+    int rows, L, heads, cap;
+    float scale2;             // softmax scale * log2(e)
+};
+
+__global__ __launch_bounds__(64) void wg_llama_attn_prefill_kernel(PrefillArgs a) {
+    __shared__ __attribute__((aligned(16))) bf16 Vs[32][136];
+    const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
+    const int qb = blockIdx.x, head = blockIdx.y, row = blockIdx.z;
+    const int H = a.heads * WG_LLAMA_HD;
+    const int past = wg_clampi(*a.past_len, 0, a.cap - a.L);
+    const int qi = qb * 32 + r;
+    const int qc = qi < a.L ? qi : a.L - 1;
+    const int qpos = past + qc;
+    const int qlast = qb * 32 + 31 < a.L ? qb * 32 + 31 : a.L - 1;
+    const int kmax = past + qlast;                      // the block's last visible key; < cap
+    bf16x8 qf[8];
+    {
+        const bf16* qp = a.q + ((long)row * a.L + qc) * a.ldq + head * WG_LLAMA_HD + 8 * h;
+#pragma unroll
+        for (int s = 0; s < 8; ++s) qf[s] = *(const bf16x8*)(qp + 16 * s);
+    }
+    f32x16 ot[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) ot[d][e] = 0.f;
+    float m = WG_NEG_BIG, l = 0.f;
+    const bf16* kb = a.kc + (long)row * a.cap * H + head * WG_LLAMA_HD;
+    const bf16* vb = a.vc + (long)row * a.cap * H + head * WG_LLAMA_HD;
+    const unsigned char* mk = a.mask + (long)row * a.cap;
+
+    for (int key0 = 0; key0 <= kmax; key0 += 32) {
+        __syncthreads();                                 // the previous step's fragment reads are done
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+            const int kr = p * 4 + (lane >> 4), key = key0 + kr, d = (lane & 15) * 8;
+            bf16x8 v;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = (bf16)0.f;
+            if (key <= kmax) v = *(const bf16x8*)(vb + (long)key * H + d);
+            *(bf16x8*)&Vs[kr][d] = v;
+        }
+        f32x16 acc;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+        {
+            const int kk = key0 + r <= kmax ? key0 + r : kmax;
+            const bf16* kp = kb + (long)kk * H + 8 * h;
+#pragma unroll
+            for (int s = 0; s < 8; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(kp + 16 * s), qf[s], acc, 0, 0, 0);
+        }
+        __syncthreads();                                 // the V image is complete
+        float sc[16], tmax = WG_NEG_BIG;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int kbase = key0 + 8 * g + 4 * h;      // key0 + 31 < cap: cap is a multiple of 64 and key0 <= kmax < cap
+            const unsigned mw = *(const unsigned*)(mk + kbase);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const bool ok = kbase + e <= qpos && ((mw >> (8 * e)) & 0xffu) != 0;
+                sc[4 * g + e] = ok ? acc[4 * g + e] * a.scale2 : WG_NEG_BIG;
+                tmax = fmaxf(tmax, sc[4 * g + e]);
+            }
+        }
+        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+        const float mn = fmaxf(m, tmax);
+        const float alpha = exp2f(m - mn);
+        m = mn;
+        bf16x8 pf[2];
+        float ps = 0.f;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const float p = sc[e] > -1.0e29f ? exp2f(sc[e] - mn) : 0.f;
+            ps += p;
+            pf[e >> 3][e & 7] = (bf16)p;
+        }
+        l = l * alpha + ps;
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) ot[d][e] *= alpha;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                bf16x8 vf;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) vf[j] = Vs[16 * ks + 8 * (j >> 2) + 4 * h + (j & 3)][32 * d + r];
+                ot[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[ks], ot[d], 0, 0, 0);
+            }
+    }
+    l += __shfl_xor(l, 32, 64);
+    const float inv = l > 0.f ? 1.0f / l : 0.f;
+    if (qi < a.L) {
+        bf16* op = a.out + ((long)row * a.L + qi) * a.ldo + head * WG_LLAMA_HD + 4 * h;
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                bf16x4 o;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = (bf16)(ot[d][4 * g + e] * inv);
+                *(bf16x4*)(op + 32 * d + 8 * g) = o;
+            }
+    }
+}
+
+extern "C" int wg_llama_attn_prefill_bf16(const void* q, long ldq, const void* k_cache, const void* v_cache, const unsigned char* mask, void* out,
+                                          long ldo, const int* past_len, int rows, int L, int heads, int cap, float scale, void* stream) {
+    WG_REQUIRE(q && k_cache && v_cache && mask && out && past_len, "llama_attn_prefill: null operand");
+    WG_REQUIRE(rows > 0 && rows <= 65535 && L > 0 && heads > 0 && heads <= 65535, "llama_attn_prefill: bad shape");
+    WG_REQUIRE(cap > 0 && cap % 64 == 0 && L <= cap, "llama_attn_prefill: capacity %d must be a multiple of 64 and >= L = %d", cap, L);
+    const long H = (long)heads * WG_LLAMA_HD;
+    WG_REQUIRE(ldq >= H && ldo >= H && ldq % 8 == 0 && ldo % 8 == 0, "llama_attn_prefill: leading dimensions too small or not multiples of 8");
+    WG_REQUIRE((((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)out) & 15) == 0 && ((uintptr_t)mask & 3) == 0,
+               "llama_attn_prefill: misaligned operand");
+    PrefillArgs a{(const bf16*)q, ldq, (const bf16*)k_cache, (const bf16*)v_cache, mask, (bf16*)out, ldo, past_len, rows, L, heads, cap,
+                  scale * 1.4426950408889634f};
+    hipLaunchKernelGGL(wg_llama_attn_prefill_kernel, dim3((unsigned)((L + 31) / 32), heads, rows), dim3(64), 0, (hipStream_t)stream, a);
+    return wg_check_launch("wg_llama_attn_prefill_bf16");
+}
+
+// ---- d. decode attention ------------------------------------------------------------------------------------------------------------
+// One query per (row, head) over keys 0 .. past_len.  WG_LLAMA_SPLITS one-wave workgroups per (row, head): split s takes the 16-key
+// groups s, s + SPLITS, ...  A lane owns 32 head dims of one key per step (K and V rows by 16-byte loads straight to registers) and a
+// private online-softmax state; the wave merges its 16 key slots by a butterfly and leaves (o[128], m, l) in fp32.  The combine kernel
+// adds the SPLITS partials of a (row, head) in index order.  P stays fp32 here.
+struct DecodeArgs {
+    const bf16* q; long ldq;
+    const bf16* kc; const bf16* vc;
+    const unsigned char* mask;
+    float* part;
+    bf16* out; long ldo;
+    const int* past_len;
+    int rows, heads, cap;
+    float scale2;
+};
+
+__global__ __launch_bounds__(64) void wg_llama_attn_decode_kernel(DecodeArgs a) {
+    const int lane = threadIdx.x, slot = lane >> 2, ds = lane & 3;
+    const int split = blockIdx.x, head = blockIdx.y, row = blockIdx.z;
+    const int H = a.heads * WG_LLAMA_HD;
+    const int nkeys = (int)wg_clampl((long)*a.past_len + 1, 1, a.cap);
+    const int dcol = head * WG_LLAMA_HD + ds * 32;
+    float q[32], o[32];
+    {
+        const bf16* qp = a.q + (long)row * a.ldq + dcol;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const bf16x8 t = *(const bf16x8*)(qp + 8 * c);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) q[8 * c + e] = (float)t[e] * a.scale2;
+        }
+    }
+#pragma unroll
+    for (int d = 0; d < 32; ++d) o[d] = 0.f;
+    float m = WG_NEG_BIG, l = 0.f;
+    const bf16* kb = a.kc + (long)row * a.cap * H + dcol;
+    const bf16* vb = a.vc + (long)row * a.cap * H + dcol;
+    const unsigned char* mk = a.mask + (long)row * a.cap;
+    for (int j0 = split * 16; j0 < nkeys; j0 += 16 * WG_LLAMA_SPLITS) {
+        const int j = j0 + slot;
+        const int jc = j < nkeys ? j : nkeys - 1;
+        const bool ok = j < nkeys && mk[jc] != 0;
+        const bf16* kp = kb + (long)jc * H;
+        const bf16* vp = vb + (long)jc * H;
+        bf16x8 kk[4], vv[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { kk[c] = *(const bf16x8*)(kp + 8 * c); vv[c] = *(const bf16x8*)(vp + 8 * c); }
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s += q[8 * c + e] * (float)kk[c][e];
+        s += __shfl_xor(s, 1, 64);
+        s += __shfl_xor(s, 2, 64);
+        if (ok) {
+            const float mn = fmaxf(m, s);
+            const float alpha = exp2f(m - mn), p = exp2f(s - mn);
+            m = mn;
+            l = l * alpha + p;
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) o[8 * c + e] = o[8 * c + e] * alpha + p * (float)vv[c][e];
+        }
+    }
+#pragma unroll
+    for (int w = 4; w < 64; w <<= 1) {
+        const float m2 = __shfl_xor(m, w, 64), l2 = __shfl_xor(l, w, 64);
+        const float mn = fmaxf(m, m2);
+        const float a1 = exp2f(m - mn), a2 = exp2f(m2 - mn);
+        l = l * a1 + l2 * a2;
+#pragma unroll
+        for (int d = 0; d < 32; ++d) {
+            const float o2 = __shfl_xor(o[d], w, 64);
+            o[d] = o[d] * a1 + o2 * a2;
+        }
+        m = mn;
+    }
+    if (slot == 0) {
+        float* pp = a.part + (((long)row * a.heads + head) * WG_LLAMA_SPLITS + split) * WG_LLAMA_PART;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) *(f32x4*)(pp + ds * 32 + 4 * c) = (f32x4){o[4 * c], o[4 * c + 1], o[4 * c + 2], o[4 * c + 3]};
+        if (ds == 0) { pp[128] = m; pp[129] = l; }
+    }
+}
+
+__global__ __launch_bounds__(128) void wg_llama_attn_combine_kernel(DecodeArgs a) {
+    const int d = threadIdx.x, head = blockIdx.x, row = blockIdx.y;
+    const float* pp = a.part + ((long)row * a.heads + head) * WG_LLAMA_SPLITS * WG_LLAMA_PART;
+    float mx = WG_NEG_BIG;
+#pragma unroll
+    for (int s = 0; s < WG_LLAMA_SPLITS; ++s) mx = fmaxf(mx, pp[s * WG_LLAMA_PART + 128]);
+    float l = 0.f, o = 0.f;
+#pragma unroll
+    for (int s = 0; s < WG_LLAMA_SPLITS; ++s) {
+        const float w = exp2f(pp[s * WG_LLAMA_PART + 128] - mx);
+        l += pp[s * WG_LLAMA_PART + 129] * w;
+        o += pp[s * WG_LLAMA_PART + d] * w;
+    }
+    a.out[(long)row * a.ldo + head * WG_LLAMA_HD + d] = (bf16)(l > 0.f ? o / l : 0.f);
+}
+
+extern "C" long wg_llama_attn_decode_workspace_floats(int rows, int heads) {
+    return (long)(rows > 0 ? rows : 0) * (heads > 0 ? heads : 0) * WG_LLAMA_SPLITS * WG_LLAMA_PART;
+}
+
+extern "C" int wg_llama_attn_decode_bf16(const void* q, long ldq, const void* k_cache, const void* v_cache, const unsigned char* mask,
+                                         float* workspace, long workspace_floats, void* out, long ldo, const int* past_len, int rows, int heads,
+                                         int cap, float scale, void* stream) {
+    WG_REQUIRE(q && k_cache && v_cache && mask && workspace && out && past_len, "llama_attn_decode: null operand");
+    WG_REQUIRE(rows > 0 && rows <= 65535 && heads > 0 && heads <= 65535, "llama_attn_decode: bad shape");
+    WG_REQUIRE(cap > 0 && cap % 64 == 0, "llama_attn_decode: cache capacity %d must be a positive multiple of 64", cap);
+    const long H = (long)heads * WG_LLAMA_HD;
+    WG_REQUIRE(ldq >= H && ldo >= H && ldq % 8 == 0, "llama_attn_decode: leading dimensions too small or not multiples of 8");
+    WG_REQUIRE(workspace_floats >= wg_llama_attn_decode_workspace_floats(rows, heads), "llama_attn_decode: workspace too small");
+    WG_REQUIRE((((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)workspace) & 15) == 0, "llama_attn_decode: misaligned operand");
+    DecodeArgs a{(const bf16*)q, ldq, (const bf16*)k_cache, (const bf16*)v_cache, mask, workspace, (bf16*)out, ldo, past_len, rows, heads, cap,
+                 scale * 1.4426950408889634f};
+    hipLaunchKernelGGL(wg_llama_attn_decode_kernel, dim3(WG_LLAMA_SPLITS, heads, rows), dim3(64), 0, (hipStream_t)stream, a);
+    int rc = wg_check_launch("wg_llama_attn_decode_bf16");
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(wg_llama_attn_combine_kernel, dim3(heads, rows), dim3(128), 0, (hipStream_t)stream, a);
+    return wg_check_launch("wg_llama_attn_decode_bf16(combine)");
+}
+
+// ---- e. decode GEMV -----------------------------------------------------------------------------------------------------------------
+// out[m][n] = sum_k xh[m][k] W[n][k] for M <= 8 rows; every weight element is read once, by non-temporal 16-byte loads straight to
+// registers (no LDS on the weight path).  A wave owns 4 weight rows at a time (pair mode: 2 gate + 2 up rows); lane l takes the
+// 8-element pieces l, l + 64, ... of each row, multiplies them with the matching pieces of the M input rows (those come from L2)
+// and the wave adds its 64 lane sums by a fixed butterfly.  (Fewer rows per wave where N is small, i.e. more waves per CU, was
+// measured on the 7B shapes: within 4 % for o_proj, down_proj and the SwiGLU pair, and 30 % slower for the q | k | v launch, whose
+// every workgroup repeats the RMSNorm prologue; profiles/llm_generate.md.)  fp32 throughout; the only rounding is that of the output.
+//   segments   up to three weight matrices (W_i [N_i, K]) are the column ranges [0, N_0), [N_0, N_0 + N_1), ... of one output
+//   norm       xh = x * rstd(x row) * gamma, not rounded; every workgroup recomputes the M values of rstd (M K reads from L2)
+//   residual   out = res + acc (res may be out)
+//   pair       out[n] = silu(W_0[n] . xh) * (W_1[n] . xh)
+//   out_f32    fp32 output (the logits)
+struct GemvArgs {
+    const bf16* x; long ldx;
+    const bf16* w[3]; int n[3];
+    int K;
+    const bf16* gamma; float eps;
+    const bf16* res; long ldr;
+    void* out; long ldo;
+    int out_f32;
+};
+
+template <int M, bool PAIR>
+__global__ __launch_bounds__(256) void wg_llama_gemv_kernel(GemvArgs a) {
+    constexpr int R = 4;                    // weight rows in flight per wave
+    constexpr int RO = PAIR ? 2 : 4;        // output columns per wave
+    __shared__ float red[4][8];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int K = a.K;
+    float rstd[M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) rstd[m] = 1.f;
+    if (a.gamma) {
+        float ss[M];
+#pragma unroll
+        for (int m = 0; m < M; ++m) ss[m] = 0.f;
+        for (int k = tid * 8; k < K; k += 2048) {
+#pragma unroll
+            for (int m = 0; m < M; ++m) {
+                const bf16x8 t = *(const bf16x8*)(a.x + (long)m * a.ldx + k);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) ss[m] += (float)t[e] * (float)t[e];
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            const float t = wg_wave_sum(ss[m]);
+            if (lane == 0) red[wave][m] = t;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < M; ++m) rstd[m] = 1.0f / sqrtf(((red[0][m] + red[1][m]) + (red[2][m] + red[3][m])) / (float)K + a.eps);
+    }
+    const int ntot = PAIR ? a.n[0] : a.n[0] + a.n[1] + a.n[2];
+    const int n0 = (blockIdx.x * 4 + wave) * RO;
+    if (n0 >= ntot) return;                 // (after the only barrier)
+    const bf16* wp[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        if constexpr (PAIR) {
+            const int n = n0 + (r & 1) < ntot ? n0 + (r & 1) : ntot - 1;
+            wp[r] = a.w[r >> 1] + (long)n * K;
+        } else {
+            int n = n0 + r < ntot ? n0 + r : ntot - 1;
+            int sgm = 0;
+            if (n >= a.n[0]) { n -= a.n[0]; sgm = 1; if (n >= a.n[1]) { n -= a.n[1]; sgm = 2; } }
+            wp[r] = a.w[sgm] + (long)n * K;
+        }
+    }
+    float acc[R][M];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int m = 0; m < M; ++m) acc[r][m] = 0.f;
+#pragma unroll 2
+    for (int k = lane * 8; k < K; k += 512) {
+        u32x4 wv[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) wv[r] = __builtin_nontemporal_load((const u32x4*)(wp[r] + k));
+        float g[8];
+        if (a.gamma) {
+            const bf16x8 t = *(const bf16x8*)(a.gamma + k);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) g[e] = (float)t[e];
+        }
+        float xf[M][8];
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            const bf16x8 t = *(const bf16x8*)(a.x + (long)m * a.ldx + k);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) xf[m][e] = a.gamma ? (float)t[e] * rstd[m] * g[e] : (float)t[e];
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const bf16x8 wb = __builtin_bit_cast(bf16x8, wv[r]);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float wf = (float)wb[e];
+#pragma unroll
+                for (int m = 0; m < M; ++m) acc[r][m] += xf[m][e] * wf;
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int m = 0; m < M; ++m) acc[r][m] = wg_wave_sum(acc[r][m]);
+    if (lane != 0) return;
+#pragma unroll
+    for (int c = 0; c < RO; ++c) {
+        const int n = n0 + c;
+        if (n >= ntot) break;
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            float v;
+            if constexpr (PAIR) {
+                const float gt = acc[c][m], up = acc[2 + c][m];
+                v = gt / (1.0f + __expf(-gt)) * up;
+            } else {
+                v = acc[c][m];
+            }
+            if (a.res) v += (float)a.res[(long)m * a.ldr + n];
+            if (a.out_f32) ((float*)a.out)[(long)m * a.ldo + n] = v;
+            else ((bf16*)a.out)[(long)m * a.ldo + n] = (bf16)v;
+        }
+    }
+}
+
+template <bool PAIR> static void wg_llama_gemv_launch(const GemvArgs& a, int M, unsigned blocks, hipStream_t st) {
+    switch (M) {
+        case 1: hipLaunchKernelGGL((wg_llama_gemv_kernel<1, PAIR>), dim3(blocks), dim3(256), 0, st, a); break;
+        case 2: hipLaunchKernelGGL((wg_llama_gemv_kernel<2, PAIR>), dim3(blocks), dim3(256), 0, st, a); break;
+        case 3: hipLaunchKernelGGL((wg_llama_gemv_kernel<3, PAIR>), dim3(blocks), dim3(256), 0, st, a); break;
+        case 4: hipLaunchKernelGGL((wg_llama_gemv_kernel<4, PAIR>), dim3(blocks), dim3(256), 0, st, a); break;
+        case 5: hipLaunchKernelGGL((wg_llama_gemv_kernel<5, PAIR>), dim3(blocks), dim3(256), 0, st, a); break;
+        case 6: hipLaunchKernelGGL((wg_llama_gemv_kernel<6, PAIR>), dim3(blocks), dim3(256), 0, st, a); break;
+        case 7: hipLaunchKernelGGL((wg_llama_gemv_kernel<7, PAIR>), dim3(blocks), dim3(256), 0, st, a); break;
+        default: hipLaunchKernelGGL((wg_llama_gemv_kernel<8, PAIR>), dim3(blocks), dim3(256), 0, st, a); break;
+    }
+}
+
+extern "C" int wg_llama_gemv_bf16(const void* x, long ldx, const void* w0, int n0, const void* w1, int n1, const void* w2, int n2, int K,
+                                  const void* gamma, float eps, const void* residual, long ldr, void* out, long ldo, int out_f32, int pair, int M,
+                                  void* stream) {
+    WG_REQUIRE(x && w0 && out, "llama_gemv: null operand");
+    WG_REQUIRE(M >= 1 && M <= 8, "llama_gemv: M = %d rows (1 .. 8)", M);
+    WG_REQUIRE(K > 0 && K % 128 == 0, "llama_gemv: K = %d must be a positive multiple of 128", K);
+    WG_REQUIRE(n0 >= 1 && n1 >= 0 && n2 >= 0 && (w1 || n1 == 0) && (w2 || n2 == 0) && (n1 > 0 || n2 == 0), "llama_gemv: bad weight segments");
+    WG_REQUIRE(!pair || (w1 && n1 == n0 && n2 == 0), "llama_gemv: pair mode takes two segments of equal N");
+    const long ntot = pair ? n0 : (long)n0 + n1 + n2;
+    WG_REQUIRE(ntot < (1L << 30), "llama_gemv: too many output columns");
+    WG_REQUIRE(ldx >= K && ldx % 8 == 0 && ldo >= ntot && (!residual || ldr >= ntot), "llama_gemv: leading dimensions too small (or ldx not a multiple of 8)");
+    WG_REQUIRE((((uintptr_t)x | (uintptr_t)w0 | (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)gamma) & 15) == 0, "llama_gemv: misaligned operand");
+    GemvArgs a{(const bf16*)x, ldx, {(const bf16*)w0, (const bf16*)w1, (const bf16*)w2}, {n0, n1, n2}, K, (const bf16*)gamma, eps,
+               (const bf16*)residual, ldr, out, ldo, out_f32};
+    const int per_block = 4 * (pair ? 2 : 4);
+    const unsigned blocks = (unsigned)((ntot + per_block - 1) / per_block);
+    if (pair) wg_llama_gemv_launch<true>(a, M, blocks, (hipStream_t)stream);
+    else wg_llama_gemv_launch<false>(a, M, blocks, (hipStream_t)stream);
+    return wg_check_launch("wg_llama_gemv_bf16");
+}
+
+// ---- SiLU(gate) * up on a [M, 2 I] buffer (gate | up), the prefill's MLP middle ------------------------------------------------------
+__global__ __launch_bounds__(256) void wg_llama_silu_mul_kernel(const bf16* gu, long ldgu, bf16* out, long ldo, int M, int I) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const int per = I / 8;
+    if (i >= (long)M * per) return;
+    const int m = (int)(i / per), c = (int)(i % per) * 8;
+    const bf16x8 g = *(const bf16x8*)(gu + (long)m * ldgu + c), u = *(const bf16x8*)(gu + (long)m * ldgu + I + c);
+    bf16x8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float gt = (float)g[e];
+        o[e] = (bf16)(gt / (1.0f + __expf(-gt)) * (float)u[e]);
+    }
+    *(bf16x8*)(out + (long)m * ldo + c) = o;
+}
+
+extern "C" int wg_llama_silu_mul_bf16(const void* gate_up, long ldgu, void* out, long ldo, int M, int I, void* stream) {
+    WG_REQUIRE(gate_up && out, "llama_silu_mul: null operand");
+    WG_REQUIRE(M > 0 && I > 0 && I % 8 == 0, "llama_silu_mul: bad shape (M %d, I %d; I must be a multiple of 8)", M, I);
+    WG_REQUIRE(ldgu >= 2L * I && ldo >= I && ldgu % 8 == 0 && ldo % 8 == 0, "llama_silu_mul: leading dimensions too small or not multiples of 8");
+    WG_REQUIRE((((uintptr_t)gate_up | (uintptr_t)out) & 15) == 0, "llama_silu_mul: misaligned operand");
+    const long total = (long)M * (I / 8);
+    hipLaunchKernelGGL(wg_llama_silu_mul_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16*)gate_up, ldgu,
+                       (bf16*)out, ldo, M, I);
+    return wg_check_launch("wg_llama_silu_mul_bf16");
+}
+
+// ---- f. token pick ------------------------------------------------------------------------------------------------------------------
+// One 1024-thread block (the rows share the state words, so one block owns them).  Per row: argmax of the fp32 logits, lowest index on
+// a tie; a finished row emits pad, finished |= (token == eos) (eos < 0: no eos, no pad substitution); tokens[row][n_new] = token; the
+// token's embedding row -> x_next[row]; mask[row][past_len + 1] = 1.  Then past_len and n_new move on by one -- past_len not beyond
+// cap - 1, n_new not beyond tok_cap (a token that has no slot is not written).
+struct PickArgs {
+    const float* logits; long ldl;
+    const bf16* embed; int n_embed;
+    bf16* x_next; long ldx;
+    long long* tokens; int tok_cap;
+    int* finished;
+    unsigned char* mask;
+    int* state;               // {past_len, n_new}
+    int eos, pad;
+    int rows, V, H, cap;
+};
+
+__global__ __launch_bounds__(1024) void wg_llama_pick_token_kernel(PickArgs a) {
+    __shared__ float bv[1024];
+    __shared__ int bi[1024];
+    __shared__ int tok[8];
+    const int tid = threadIdx.x;
+    const int past = a.state[0], nn = a.state[1];
+    for (int row = 0; row < a.rows; ++row) {
+        const float* lg = a.logits + (long)row * a.ldl;
+        float best = -INFINITY;
+        int idx = 0x7fffffff;
+        for (int i = tid; i < a.V; i += 1024) {
+            const float v = lg[i];
+            if (v > best || idx == 0x7fffffff) { best = v; idx = i; }     // strictly greater: the lowest index of a thread's run wins
+        }
+        bv[tid] = best;
+        bi[tid] = idx;
+        __syncthreads();
+        for (int w = 512; w > 0; w >>= 1) {
+            if (tid < w) {
+                const float v2 = bv[tid + w];
+                const int i2 = bi[tid + w];
+                if (i2 != 0x7fffffff && (bi[tid] == 0x7fffffff || v2 > bv[tid] || (v2 == bv[tid] && i2 < bi[tid]))) { bv[tid] = v2; bi[tid] = i2; }
+            }
+            __syncthreads();
+        }
+        if (tid == 0) {
+            int t = wg_clampi(bi[0], 0, a.V - 1);
+            if (a.eos >= 0) {
+                int fin = a.finished[row];
+                if (fin) t = a.pad;
+                fin |= (t == a.eos);
+                a.finished[row] = fin;
+            }
+            tok[row] = t;
+            if (nn >= 0 && nn < a.tok_cap) a.tokens[(long)row * a.tok_cap + nn] = t;
+            if (past >= -1 && past < a.cap - 1) a.mask[(long)row * a.cap + past + 1] = 1;
+        }
+        __syncthreads();
+    }
+    for (int row = 0; row < a.rows; ++row) {
+        const bf16* src = a.embed + (long)wg_clampi(tok[row], 0, a.n_embed - 1) * a.H;
+        for (int k = tid * 8; k < a.H; k += 8192) *(bf16x8*)(a.x_next + (long)row * a.ldx + k) = *(const bf16x8*)(src + k);
+    }
+    if (tid == 0) {
+        if (past >= -1 && past < a.cap - 1) a.state[0] = past + 1;
+        if (nn >= 0 && nn < a.tok_cap) a.state[1] = nn + 1;
+    }
+}
+
+extern "C" int wg_llama_pick_token(const float* logits, long ldl, const void* embed, int n_embed, void* x_next, long ldx, long long* tokens,
+                                   int tok_cap, int* finished, unsigned char* mask, int* state, int eos, int pad, int rows, int V, int H, int cap,
+                                   void* stream) {
+    WG_REQUIRE(logits && embed && x_next && tokens && finished && mask && state, "llama_pick_token: null operand");
+    WG_REQUIRE(rows >= 1 && rows <= 8, "llama_pick_token: rows = %d (1 .. 8)", rows);
+    WG_REQUIRE(V >= 1 && n_embed >= V && H > 0 && H % 8 == 0 && tok_cap >= 1, "llama_pick_token: bad shape (V %d, embedding rows %d, H %d)", V, n_embed, H);
+    WG_REQUIRE(cap > 0 && cap % 64 == 0, "llama_pick_token: cache capacity %d must be a positive multiple of 64", cap);
+    WG_REQUIRE(ldl >= V && ldx >= H && ldx % 8 == 0, "llama_pick_token: leading dimensions too small");
+    WG_REQUIRE(eos < 0 || (pad >= 0 && pad < n_embed), "llama_pick_token: pad id %d outside the embedding table", pad);
+    WG_REQUIRE((((uintptr_t)embed | (uintptr_t)x_next) & 15) == 0, "llama_pick_token: misaligned operand");
+    PickArgs a{logits, ldl, (const bf16*)embed, n_embed, (bf16*)x_next, ldx, tokens, tok_cap, finished, mask, state, eos, pad, rows, V, H, cap};
+    hipLaunchKernelGGL(wg_llama_pick_token_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
+    return wg_check_launch("wg_llama_pick_token");
+}

@@ -1,0 +1,258 @@
+"""The language model's generate path on the HIP kernels of csrc/llama.hip: a causal prefill through the bf16 GEMMs and a KV-cache decode
+step of weight-streaming GEMVs, captured once into a HIP graph and replayed per token.  Opt-in (walkgptForCausalLM.enable_hip_llm); the
+runner reads the `transformers` LlamaForCausalLM's own weight tensors -- nothing is packed or copied.
+
+Decode step, per layer: gemv (RMSNorm -> q | k | v), rope + cache write, decode attention (+ its combine), gemv (o_proj + residual), gemv (RMSNorm ->
+SwiGLU), gemv (down_proj + residual); then the final RMSNorm into the hidden-state buffer, the lm_head gemv and the device-side token pick.  After
+the pick a step needs nothing from the host: the host only looks at the tokens every `sync_every` steps to see whether every row has finished.
+
+Memory kept between calls (one (rows, cap) signature only): the KV cache, 2 * layers * rows * cap * hidden * 2 bytes (a 7B model at cap 896:
+0.47 GB per row), the hidden-state buffer rows * cap * hidden * 2 bytes and a few row-sized work buffers."""
+import math
+
+import torch
+from torch import nn
+
+from . import ops
+
+BF16 = torch.bfloat16
+MAX_ROWS = 8
+
+
+def _rope_params(config):
+    p = getattr(config, "rope_parameters", None) or getattr(config, "rope_scaling", None) or {}
+    theta = p.get("rope_theta", getattr(config, "rope_theta", None))
+    return (10000.0 if theta is None else float(theta)), p.get("rope_type", p.get("type", "default")) or "default"
+
+
+def rope_table(config, max_pos):
+    """cos, sin fp32 [max_pos, 64] of the default rope type, by LlamaRotaryEmbedding's formula: inv_freq = theta^(-2i / 128) in fp32, angle = position
+    * inv_freq in fp32 (the two halves of transformers' [.., 128] table are equal, so 64 columns hold all of it)."""
+    theta, _ = _rope_params(config)
+    inv_freq = 1.0 / (theta ** (torch.arange(0, 128, 2, dtype=torch.float) / 128))
+    freqs = torch.arange(max_pos, dtype=torch.float)[:, None] * inv_freq[None, :]
+    return freqs.cos().contiguous(), freqs.sin().contiguous()
+
+
+def trimmed_length(tokens, eos, max_new_tokens):
+    """How many of the emitted tokens `_generate` returns: it stops after the step at which every row has emitted eos (a finished row goes on
+    emitting pad), else after max_new_tokens.  tokens: int64 [rows, steps] (steps <= max_new_tokens) -> n in 1 .. max_new_tokens, or None when
+    the steps seen so far do not decide it yet."""
+    steps = tokens.shape[1]
+    if eos is not None and steps > 0:
+        hit = tokens == eos
+        if bool(hit.any(1).all()):
+            return int(hit.int().argmax(1).max()) + 1
+    return max_new_tokens if steps >= max_new_tokens else None
+
+
+class _Buffers:
+    pass
+
+
+class LlamaHipRunner:
+    def __init__(self, llm):
+        ok, why = self.supports(llm)
+        if not ok:
+            raise ValueError("LlamaHipRunner: " + why)
+        self.llm = llm
+        cfg = llm.config
+        self.hidden, self.inter, self.heads = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
+        self.eps = float(cfg.rms_norm_eps)
+        self.scale = 1.0 / math.sqrt(128.0)
+        self._buf = None
+        self._graph = None
+        self.captures = 0            # how many times a decode step has been captured (tests: a second generate replays)
+
+    # -- what the kernels cover ------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def supports(llm):
+        cfg = getattr(llm, "config", None)
+        if cfg is None or not hasattr(llm, "model") or not hasattr(llm, "lm_head"):
+            return False, "not a LlamaForCausalLM-shaped module (config, model, lm_head)"
+        heads = cfg.num_attention_heads
+        hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // heads
+        if hd != 128:
+            return False, "head_dim %d: the attention kernels are built for 128" % hd
+        if getattr(cfg, "num_key_value_heads", heads) != heads:
+            return False, "grouped-query attention (num_key_value_heads %s != num_attention_heads %d) is not built" % (cfg.num_key_value_heads, heads)
+        if getattr(cfg, "attention_bias", False) or getattr(cfg, "mlp_bias", False):
+            return False, "attention / MLP bias is not built"
+        if getattr(cfg, "hidden_act", "silu") != "silu":
+            return False, "hidden_act %r: only silu" % (cfg.hidden_act,)
+        if _rope_params(cfg)[1] != "default":
+            return False, "rope scaling (%s) is not built: default rope only" % _rope_params(cfg)[1]
+        if cfg.hidden_size % 128 or cfg.intermediate_size % 128 or cfg.hidden_size != heads * 128:
+            return False, "hidden size %d / intermediate size %d must be multiples of 128 (hidden = heads * 128)" % (cfg.hidden_size, cfg.intermediate_size)
+        tensors = [llm.get_input_embeddings().weight, llm.model.norm.weight]
+        linears = [("lm_head", llm.lm_head)]
+        for i, layer in enumerate(llm.model.layers):
+            tensors += [layer.input_layernorm.weight, layer.post_attention_layernorm.weight]
+            linears += [("layers.%d.self_attn.%s" % (i, n), getattr(layer.self_attn, n)) for n in ("q_proj", "k_proj", "v_proj", "o_proj")]
+            linears += [("layers.%d.mlp.%s" % (i, n), getattr(layer.mlp, n)) for n in ("gate_proj", "up_proj", "down_proj")]
+        for name, m in linears:
+            if type(m) is not nn.Linear:
+                return False, "%s is a %s, not a plain nn.Linear: merge the adapters first" % (name, type(m).__name__)
+            if m.bias is not None:
+                return False, "%s has a bias: not built" % name
+            tensors.append(m.weight)
+        for t in tensors:
+            if t.dtype != BF16 or not t.is_cuda:
+                return False, "weights must be bf16 on a GPU (found %s on %s)" % (str(t.dtype).replace("torch.", ""), t.device)
+            if not t.is_contiguous():
+                return False, "weights must be contiguous"
+        return True, ""
+
+    # -- weights -----------------------------------------------------------------------------------------------------------------------------
+    def _layers(self):
+        out = []
+        for layer in self.llm.model.layers:
+            a, m = layer.self_attn, layer.mlp
+            out.append((layer.input_layernorm.weight, a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, a.o_proj.weight,
+                        layer.post_attention_layernorm.weight, m.gate_proj.weight, m.up_proj.weight, m.down_proj.weight))
+        return out
+
+    def _weight_key(self):
+        ts = [t for lw in self._layers() for t in lw] + [self.llm.model.norm.weight, self.llm.lm_head.weight, self.llm.get_input_embeddings().weight]
+        return tuple((t.data_ptr(), t._version, t.dtype) for t in ts)
+
+    # -- buffers of one (rows, cap) signature ------------------------------------------------------------------------------------------------
+    def _buffers(self, rows, cap, dev):
+        b = self._buf
+        if b is not None and (b.rows, b.cap, b.dev) == (rows, cap, dev):
+            return b
+        self._buf = self._graph = None           # the old signature's cache and graph go first: two caches need not fit
+        b = _Buffers()
+        b.rows, b.cap, b.dev = rows, cap, dev
+        H, I, V = self.hidden, self.inter, self.llm.lm_head.weight.shape[0]
+        e = lambda *s, dtype=BF16: torch.empty(*s, device=dev, dtype=dtype)
+        b.kv = [(e(rows, cap, H), e(rows, cap, H)) for _ in self.llm.model.layers]
+        b.hs = e(rows, cap, H)
+        b.mask = torch.zeros(rows, cap, device=dev, dtype=torch.uint8)
+        b.state = torch.zeros(2, device=dev, dtype=torch.int32)      # {past_len, n_new}
+        b.zero = torch.zeros(1, device=dev, dtype=torch.int32)
+        b.finished = torch.zeros(rows, device=dev, dtype=torch.int32)
+        b.tokens = torch.zeros(rows, cap, device=dev, dtype=torch.int64)
+        b.x, b.qkv, b.q, b.attn, b.act = e(rows, H), e(rows, 3 * H), e(rows, H), e(rows, H), e(rows, I)
+        b.x.zero_()
+        b.logits = e(rows, V, dtype=torch.float32)
+        b.ws = ops.llama_attn_decode_workspace(rows, self.heads, dev)
+        cos, sin = rope_table(self.llm.config, cap)
+        b.cos, b.sin = cos.to(dev), sin.to(dev)
+        self._buf = b
+        return b
+
+    # -- prefill -----------------------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def prefill(self, inputs_embeds, attention_mask, cap=None, all_logits=False):
+        """-> (post-model.norm hidden states [rows, L0, H] bf16, fp32 logits [rows, V] of the last position or [rows, L0, V] of all).  Fills the KV
+        cache of the (rows, cap) buffers; all_logits runs the lm_head 8 rows at a time (a checking aid, not a fast path)."""
+        rows, L0, H = inputs_embeds.shape
+        if rows > MAX_ROWS:
+            raise NotImplementedError("LlamaHipRunner: %d rows (the decode GEMV takes at most %d)" % (rows, MAX_ROWS))
+        assert H == self.hidden and inputs_embeds.dtype == BF16 and inputs_embeds.is_cuda
+        cap = (L0 + 63) // 64 * 64 if cap is None else cap
+        assert cap % 64 == 0 and cap >= L0
+        b = self._buffers(rows, cap, inputs_embeds.device)
+        b.mask.zero_()
+        b.mask[:, :L0] = attention_mask.to(torch.uint8)
+        M, I, heads = rows * L0, self.inter, self.heads
+        h = inputs_embeds.reshape(M, H).contiguous()
+        qkv = torch.empty(M, 3 * H, device=h.device, dtype=BF16)
+        q = torch.empty(M, H, device=h.device, dtype=BF16)
+        gu = torch.empty(M, 2 * I, device=h.device, dtype=BF16)
+        for (ln1, wq, wk, wv, wo, ln2, wg, wu, wd), (kc, vc) in zip(self._layers(), b.kv):
+            xn = ops.rmsnorm(h, ln1, self.eps)
+            for i, w in enumerate((wq, wk, wv)):
+                ops.linear(xn, w, out=qkv[:, i * H:(i + 1) * H])
+            ops.llama_rope_cache(qkv, b.cos, b.sin, b.zero, q, kc, vc, rows, L0, heads)
+            att = ops.llama_attn_prefill(q, kc, vc, b.mask, b.zero, L0, heads, self.scale)
+            h = ops.linear(att, wo, residual=h)
+            xn = ops.rmsnorm(h, ln2, self.eps)
+            ops.linear(xn, wg, out=gu[:, :I])
+            ops.linear(xn, wu, out=gu[:, I:])
+            h = ops.linear(ops.llama_silu_mul(gu), wd, residual=h)
+        norm_w, head_w = self.llm.model.norm.weight, self.llm.lm_head.weight
+        h3 = h.view(rows, L0, H)
+        for r in range(rows):
+            ops.rmsnorm(h3[r], norm_w, self.eps, out=b.hs[r, :L0])
+        hidden = b.hs[:, :L0]
+        ops.llama_gemv(h3[:, -1], [head_w], gamma=norm_w, eps=self.eps, out=b.logits, out_f32=True)
+        if not all_logits:
+            return hidden, b.logits
+        logits = torch.empty(M, head_w.shape[0], device=h.device, dtype=torch.float32)
+        for m0 in range(0, M, MAX_ROWS):
+            ops.llama_gemv(h[m0:m0 + MAX_ROWS], [head_w], gamma=norm_w, eps=self.eps, out=logits[m0:m0 + MAX_ROWS], out_f32=True)
+        return hidden, logits.view(rows, L0, -1)
+
+    # -- one decode step: a linear chain of launches on the current stream, no allocation, no host read ---------------------------------------
+    def _decode_step(self, b, eos, pad):
+        past, heads = b.state[0:1], self.heads
+        for (ln1, wq, wk, wv, wo, ln2, wg, wu, wd), (kc, vc) in zip(self._layers(), b.kv):
+            ops.llama_gemv(b.x, [wq, wk, wv], gamma=ln1, eps=self.eps, out=b.qkv)
+            ops.llama_rope_cache(b.qkv, b.cos, b.sin, past, b.q, kc, vc, b.rows, 1, heads)
+            ops.llama_attn_decode(b.q, kc, vc, b.mask, past, heads, self.scale, workspace=b.ws, out=b.attn)
+            ops.llama_gemv(b.attn, [wo], residual=b.x, out=b.x)
+            ops.llama_gemv(b.x, [wg, wu], gamma=ln2, eps=self.eps, out=b.act, pair=True)
+            ops.llama_gemv(b.act, [wd], residual=b.x, out=b.x)
+        norm_w = self.llm.model.norm.weight
+        ops.rmsnorm(b.x, norm_w, self.eps, out=b.hs, slot=past)           # the hidden state of the token at position past_len
+        ops.llama_gemv(b.x, [self.llm.lm_head.weight], gamma=norm_w, eps=self.eps, out=b.logits, out_f32=True)
+        self._pick(b, eos, pad)
+
+    def _pick(self, b, eos, pad):
+        ops.llama_pick_token(b.logits, self.llm.get_input_embeddings().weight, b.x, b.tokens, b.finished, b.mask, b.state, eos, pad)
+
+    def _captured_step(self, b, eos, pad):
+        """The decode step of these buffers as a HIP graph, captured on first use and again whenever a weight it reads has moved or changed
+        (the key carries data_ptr, _version and dtype of every one).  Warm-up and capture run on a stream of the graph's own; they advance
+        the device state, so this is called BEFORE the prefill that sets it."""
+        key = (eos, pad, self._weight_key())
+        if self._graph is not None and self._graph[1] == key:
+            return self._graph[0]
+        self._graph = None
+        b.state.zero_()
+        cap_stream = torch.cuda.Stream()
+        cap_stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(cap_stream):
+            for _ in range(2):
+                self._decode_step(b, eos, pad)
+        torch.cuda.current_stream().wait_stream(cap_stream)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=cap_stream):
+            self._decode_step(b, eos, pad)
+        self._graph = (g, key, cap_stream)
+        self.captures += 1
+        return g
+
+    # -- generate ----------------------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def generate(self, inputs_embeds, attention_mask, max_new_tokens, eos=None, pad=None, graph=True, sync_every=8):
+        """walkgptForCausalLM._generate's contract: -> (new token ids [rows, n] int64, last-layer (post-norm) hidden states of the prompt and of
+        every generated token that was fed back, [rows, L0 + n - 1, H]).  Greedy; rows that have emitted eos go on emitting pad; n ends at the
+        step at which every row has finished, whatever sync_every is."""
+        rows, L0, H = inputs_embeds.shape
+        if rows > MAX_ROWS:
+            raise NotImplementedError("LlamaHipRunner: %d rows (the decode GEMV takes at most %d)" % (rows, MAX_ROWS))
+        assert max_new_tokens >= 1 and sync_every >= 1
+        pad = eos if pad is None else pad
+        cap = (L0 + max_new_tokens + 63) // 64 * 64
+        b = self._buffers(rows, cap, inputs_embeds.device)
+        g = self._captured_step(b, eos, pad) if graph else None
+        self.prefill(inputs_embeds, attention_mask, cap=cap)
+        b.finished.zero_()
+        b.state.zero_()
+        b.state[0:1].fill_(L0 - 1)                 # the pick works from the position of the token whose logits it reads
+        self._pick(b, eos, pad)
+        done, n = 1, None
+        while n is None:
+            n = trimmed_length(b.tokens[:, :done].cpu(), eos, max_new_tokens)
+            if n is not None:
+                break
+            for _ in range(min(sync_every, max_new_tokens - done)):
+                if g is not None:
+                    g.replay()
+                else:
+                    self._decode_step(b, eos, pad)
+                done += 1
+        return b.tokens[:, :n].clone(), b.hs[:, :L0 + n - 1].clone()

@@ -1180,3 +1180,129 @@ def nms(boxes, scores, iou_threshold):
     _lib.check(L.wg_nms_f32(boxes.data_ptr(), order.data_ptr(), float(iou_threshold), keep.data_ptr(), n_keep.data_ptr(), ws.data_ptr(), nws, N,
                             _stream()), "wg_nms_f32")
     return keep[:int(n_keep.item())].to(torch.int64)
+
+
+# ---- the LLaMA generate path (csrc/llama.hip): thin wrappers, no allocation unless `out` is missing (they run inside a graph capture) ----------
+def rmsnorm(x, weight, eps, out=None, slot=None, slot_add=0):
+    """y = x * rsqrt(mean(x^2) + eps) * weight per row (wg_rmsnorm_rows_bf16).  slot (int32 [1] on the device): `out` is [rows, slot_cap, D] and
+    row r is written to out[r, clamp(slot + slot_add)]."""
+    _need_gpu(x, weight, out, slot)
+    assert x.dtype == _BF16 and weight.dtype == _BF16
+    M, D, ldx = _rows(x)
+    if out is None:
+        assert slot is None
+        out = torch.empty(x.shape, device=x.device, dtype=_BF16)
+    if slot is None:
+        Mo, Do, ldy = _rows(out)
+        assert (Mo, Do) == (M, D)
+        slot_cap, ybs = 0, 0
+    else:
+        assert out.dim() == 3 and out.is_contiguous() and out.shape[0] == M and out.shape[2] == D and slot.dtype == torch.int32
+        slot_cap, ldy, ybs = out.shape[1], D, out.stride(0)
+    _lib.check(_lib.lib().wg_rmsnorm_rows_bf16(x.data_ptr(), ldx, weight.data_ptr(), out.data_ptr(), ldy, M, D, float(eps), _ptr(slot), int(slot_add),
+                                               slot_cap, ybs, _stream()), "wg_rmsnorm_rows_bf16")
+    return out
+
+
+def llama_rope_cache(qkv, cos, sin, past_len, q_out, k_cache, v_cache, rows, L, heads):
+    """qkv [rows * L, 3H] -> rotated q in q_out [rows * L, H], rotated k and v into k_cache / v_cache [rows, cap, H] at positions past_len + j."""
+    _need_gpu(qkv, cos, sin, past_len, q_out, k_cache, v_cache)
+    H = heads * 128
+    assert qkv.dtype == _BF16 and qkv.shape == (rows * L, 3 * H) and q_out.shape == (rows * L, H) and q_out.dtype == _BF16
+    assert cos.dtype == torch.float32 and cos.is_contiguous() and cos.shape[1] == 64 and sin.shape == cos.shape and sin.is_contiguous()
+    assert past_len.dtype == torch.int32
+    assert k_cache.is_contiguous() and k_cache.dtype == _BF16 and k_cache.shape[0] == rows and k_cache.shape[2] == H and v_cache.shape == k_cache.shape
+    _lib.check(_lib.lib().wg_llama_rope_cache_bf16(qkv.data_ptr(), qkv.stride(0), cos.data_ptr(), sin.data_ptr(), cos.shape[0], past_len.data_ptr(),
+                                                   q_out.data_ptr(), q_out.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), rows, L, heads,
+                                                   k_cache.shape[1], _stream()), "wg_llama_rope_cache_bf16")
+    return q_out
+
+
+def _llama_cache_args(q, k_cache, v_cache, mask, past_len, heads):
+    _need_gpu(q, k_cache, v_cache, mask, past_len)
+    rows, cap, H = k_cache.shape
+    assert H == heads * 128 and q.dtype == _BF16 and k_cache.dtype == _BF16 and k_cache.is_contiguous() and v_cache.is_contiguous()
+    assert v_cache.shape == k_cache.shape and mask.dtype == torch.uint8 and mask.shape == (rows, cap) and mask.is_contiguous()
+    assert past_len.dtype == torch.int32
+    return rows, cap, H
+
+
+def llama_attn_prefill(q, k_cache, v_cache, mask, past_len, L, heads, scale, out=None):
+    """Causal + key-mask attention of q [rows * L, H] over the cache (query j at position past_len + j)."""
+    rows, cap, H = _llama_cache_args(q, k_cache, v_cache, mask, past_len, heads)
+    assert q.shape == (rows * L, H)
+    if out is None:
+        out = torch.empty(rows * L, H, device=q.device, dtype=_BF16)
+    _lib.check(_lib.lib().wg_llama_attn_prefill_bf16(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), mask.data_ptr(),
+                                                     out.data_ptr(), out.stride(0), past_len.data_ptr(), rows, L, heads, cap, float(scale),
+                                                     _stream()), "wg_llama_attn_prefill_bf16")
+    return out
+
+
+def llama_attn_decode_workspace(rows, heads, device):
+    return torch.empty(_lib.lib().wg_llama_attn_decode_workspace_floats(rows, heads), device=device, dtype=torch.float32)
+
+
+def llama_attn_decode(q, k_cache, v_cache, mask, past_len, heads, scale, workspace=None, out=None):
+    """One query per row, q [rows, H], over keys 0 .. past_len of the cache."""
+    rows, cap, H = _llama_cache_args(q, k_cache, v_cache, mask, past_len, heads)
+    assert q.shape == (rows, H)
+    if workspace is None:
+        workspace = llama_attn_decode_workspace(rows, heads, q.device)
+    if out is None:
+        out = torch.empty(rows, H, device=q.device, dtype=_BF16)
+    _lib.check(_lib.lib().wg_llama_attn_decode_bf16(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), mask.data_ptr(),
+                                                    workspace.data_ptr(), workspace.numel(), out.data_ptr(), out.stride(0), past_len.data_ptr(),
+                                                    rows, heads, cap, float(scale), _stream()), "wg_llama_attn_decode_bf16")
+    return out
+
+
+def llama_gemv(x, weights, gamma=None, eps=0.0, residual=None, out=None, out_f32=False, pair=False):
+    """x [M <= 8, K] against one to three weights [N_i, K] whose outputs sit side by side in `out` [M, sum N_i] (pair: silu(W_0 x) * (W_1 x),
+    [M, N_0]).  gamma: RMSNorm prologue; residual: added before the rounding (may be `out`)."""
+    weights = list(weights)
+    _need_gpu(x, gamma, residual, out, *weights)
+    assert x.dtype == _BF16 and 1 <= len(weights) <= 3
+    M, K, ldx = _rows(x)
+    for w in weights:
+        assert w.dtype == _BF16 and w.dim() == 2 and w.shape[1] == K and w.is_contiguous()
+    ns = [int(w.shape[0]) for w in weights] + [0] * (3 - len(weights))
+    N = ns[0] if pair else sum(ns)
+    if out is None:
+        out = torch.empty(M, N, device=x.device, dtype=torch.float32 if out_f32 else _BF16)
+    Mo, No, ldo = _rows(out)
+    assert (Mo, No) == (M, N) and out.dtype == (torch.float32 if out_f32 else _BF16)
+    assert gamma is None or (gamma.dtype == _BF16 and gamma.numel() == K and gamma.is_contiguous())
+    assert residual is None or residual.shape[-1] == N
+    ptrs = [w.data_ptr() for w in weights] + [0] * (3 - len(weights))
+    _lib.check(_lib.lib().wg_llama_gemv_bf16(x.data_ptr(), ldx, ptrs[0], ns[0], ptrs[1], ns[1], ptrs[2], ns[2], K, _ptr(gamma), float(eps),
+                                             _ptr(residual), _residual_ld(residual), out.data_ptr(), ldo, 1 if out_f32 else 0, 1 if pair else 0, M,
+                                             _stream()), "wg_llama_gemv_bf16")
+    return out
+
+
+def llama_silu_mul(gate_up, out=None):
+    """gate_up [M, 2I] (gate | up) -> silu(gate) * up [M, I]."""
+    _need_gpu(gate_up, out)
+    assert gate_up.dtype == _BF16
+    M, I2, ld = _rows(gate_up)
+    if out is None:
+        out = torch.empty(M, I2 // 2, device=gate_up.device, dtype=_BF16)
+    _lib.check(_lib.lib().wg_llama_silu_mul_bf16(gate_up.data_ptr(), ld, out.data_ptr(), _rows(out)[2], M, I2 // 2, _stream()),
+               "wg_llama_silu_mul_bf16")
+    return out
+
+
+def llama_pick_token(logits, embed, x_next, tokens, finished, mask, state, eos, pad):
+    """The greedy step on the device (wg_llama_pick_token): logits fp32 [rows, V], embed bf16 [>= V, H], x_next bf16 [rows, H], tokens int64
+    [rows, tok_cap], finished int32 [rows], mask uint8 [rows, cap], state int32 {past_len, n_new}.  eos None: no eos / pad rule."""
+    _need_gpu(logits, embed, x_next, tokens, finished, mask, state)
+    rows, V = logits.shape
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and embed.dtype == _BF16 and embed.is_contiguous()
+    assert x_next.dtype == _BF16 and x_next.shape == (rows, embed.shape[1]) and tokens.dtype == torch.int64 and tokens.is_contiguous()
+    assert finished.dtype == torch.int32 and finished.numel() == rows and mask.dtype == torch.uint8 and mask.is_contiguous() and mask.shape[0] == rows
+    assert state.dtype == torch.int32 and state.numel() >= 2 and tokens.shape[0] == rows
+    _lib.check(_lib.lib().wg_llama_pick_token(logits.data_ptr(), logits.stride(0), embed.data_ptr(), embed.shape[0], x_next.data_ptr(),
+                                              x_next.stride(0), tokens.data_ptr(), tokens.shape[1], finished.data_ptr(), mask.data_ptr(),
+                                              state.data_ptr(), -1 if eos is None else int(eos), 0 if pad is None else int(pad), rows, V,
+                                              embed.shape[1], mask.shape[1], _stream()), "wg_llama_pick_token")
