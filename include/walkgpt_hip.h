@@ -542,6 +542,15 @@ int wg_rmsnorm_rows_bf16(const void* x, long ldx, const void* w, void* y, long l
  *   [0, cap) writes no slot). */
 int wg_llama_rope_cache_bf16(const void* qkv, long ldqkv, const float* cos_table, const float* sin_table, int max_pos, const int* past_len,
                              void* q_out, long ldq, void* k_cache, void* v_cache, int rows, int L, int heads, int cap, void* stream);
+/* wg_llama_rope_cache_lora_bf16: the same with the up-projection of unmerged LoRA adapters: before the rotation (v: before the copy) the adapted
+ *   ones of q, k, v become, in fp32, x[n] + s * sum_j B[n][j] t[tok][seg * rank + j] (seg 0 / 1 / 2 = q / k / v).  b_q, b_k, b_v: [H, rank] bf16,
+ *   contiguous, each may be NULL (all NULL: wg_llama_rope_cache_bf16's result, bit for bit); t: fp32 [rows * L, 3 rank] with row stride ldt,
+ *   as wg_llama_gemv_lora_bf16 leaves it.  Checked before any pointer is read, each < 0 with "llama_rope_cache_lora" in wg_last_error():
+ *   everything wg_llama_rope_cache_bf16 checks; rank a multiple of 8 in 8 .. 64; with an adapter given: t not NULL, ldt >= 3 rank and
+ *   ldt % 4 == 0, t and every B 16-byte aligned. */
+int wg_llama_rope_cache_lora_bf16(const void* qkv, long ldqkv, const float* cos_table, const float* sin_table, int max_pos, const int* past_len,
+                                  void* q_out, long ldq, void* k_cache, void* v_cache, int rows, int L, int heads, int cap, const float* t, long ldt,
+                                  const void* b_q, const void* b_k, const void* b_v, float s_q, float s_k, float s_v, int rank, void* stream);
 /* wg_llama_attn_prefill_bf16: causal attention of L queries per row (query j at position *past_len + j) over the cached keys 0 .. position
  *   whose mask byte is set; q, out [rows * L, H]; L <= cap; the mask 4-byte aligned. */
 int wg_llama_attn_prefill_bf16(const void* q, long ldq, const void* k_cache, const void* v_cache, const unsigned char* mask, void* out, long ldo,
@@ -558,6 +567,15 @@ int wg_llama_attn_decode_bf16(const void* q, long ldq, const void* k_cache, cons
  *   out_f32: fp32 output. */
 int wg_llama_gemv_bf16(const void* x, long ldx, const void* w0, int n0, const void* w1, int n1, const void* w2, int n2, int K, const void* gamma,
                        float eps, const void* residual, long ldr, void* out, long ldo, int out_f32, int pair, int M, void* stream);
+/* wg_llama_gemv_lora_bf16: the same launch with the down-projections of unmerged LoRA adapters as further weight rows: a_i ([rank, K] bf16,
+ *   contiguous, may be NULL) belongs to segment i and reads the same xh; t[m][i * rank + j] = a_i[j] . xh[m], fp32 and not rounded, t [M, 3 rank]
+ *   with row stride ldt (the columns of an absent adapter are not written).  out is what wg_llama_gemv_bf16 gives, bit for bit.  Checked
+ *   before any pointer is read, each < 0 with "llama_gemv_lora" in wg_last_error(): everything wg_llama_gemv_bf16 checks; rank a multiple of 8 in
+ *   8 .. 64; pair != 0 (pair mode takes no adapters); an adapter on an absent segment; with an adapter given: t not NULL, ldt >= 3 rank and
+ *   ldt % 4 == 0, t and every a_i 16-byte aligned. */
+int wg_llama_gemv_lora_bf16(const void* x, long ldx, const void* w0, int n0, const void* w1, int n1, const void* w2, int n2, int K, const void* gamma,
+                            float eps, const void* residual, long ldr, void* out, long ldo, int out_f32, int pair, int M, const void* a0,
+                            const void* a1, const void* a2, int rank, float* t, long ldt, void* stream);
 /* wg_llama_silu_mul_bf16: out[m][i] = silu(gate_up[m][i]) * gate_up[m][I + i], I % 8 == 0 */
 int wg_llama_silu_mul_bf16(const void* gate_up, long ldgu, void* out, long ldo, int M, int I, void* stream);
 /* wg_llama_pick_token: per row (rows <= 8) the argmax of fp32 logits [rows, V] (lowest index on a tie); a finished row emits pad and

@@ -6,9 +6,14 @@ positions), 128 new tokens, no eos.  Per path the median of `--runs` runs of: th
 time per token, (generation - prefill) / (new - 1).  Also: the weight bytes a decode step streams / its time, as a share of the 6.29 TB/s copy rate
 measured on an MI355X.  Prints one JSON line; results belong in profiles/llm_generate.md.
 
-    python tools/bench_llm.py [--layers 32] [--rows 1] [--l0 320] [--new 128] [--runs 5] [--one-step]
+    python tools/bench_llm.py [--layers 32] [--rows 1] [--l0 320] [--new 128] [--runs 5] [--one-step] [--lora q_proj,v_proj --lora-r 8 --lora-alpha 16]
 --one-step: no timing; after a warm generation, replay ONE graphed decode step (for `rocprofv3 --kernel-trace --stats -- python tools/bench_llm.py
---one-step`, whose per-kernel table then holds that step on top of the warm-up)."""
+--one-step`, whose per-kernel table then holds that step on top of the warm-up).
+--lora: unmerged LoRA adapters.  The plain model is measured first (graphed HIP path), then stand-in adapters (tests/lora_reference.py's
+LoraLinear, the attributes of PEFT's layer; random A and random non-zero B) go onto the named projections of every layer and the same process
+measures the graphed HIP path and the stock path on the adapted model, and last the graphed HIP path with every adapter disabled (the plain
+path again, as a control for drift inside the process).  "lora" in the JSON line: prefill ms and decode ms/token of the four, each with the
+lowest and highest of its runs.  The stand-in layer comes from tests/lora_reference.py, so --lora needs the checkout's tests/ directory.  With --one-step the replayed step is the adapted model's."""
 import argparse
 import json
 import os
@@ -38,7 +43,7 @@ def build(layers, dev):
     return llm.eval()
 
 
-def timed(fn, runs):
+def timed_all(fn, runs):
     out = []
     for _ in range(runs):
         torch.cuda.synchronize()
@@ -46,7 +51,32 @@ def timed(fn, runs):
         fn()
         torch.cuda.synchronize()
         out.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(out)
+    return out
+
+
+def timed(fn, runs):
+    return statistics.median(timed_all(fn, runs))
+
+
+def measure(prefill, generate, runs, new):
+    """-> (tokens of the warm-up generation, {prefill_ms, decode_ms_per_token: median, lowest, highest of the runs}); a run's decode time per
+    token is (its generation - the median prefill) / (new - 1)"""
+    prefill()
+    tokens = generate()[0]                         # warm-up (and, for the graphed path, the capture)
+    p, t = timed_all(prefill, runs), timed_all(generate, runs)
+    pm = statistics.median(p)
+    d = [(x - pm) / max(1, new - 1) for x in t]
+    stat = lambda v, nd: {"median": round(statistics.median(v), nd), "min": round(min(v), nd), "max": round(max(v), nd)}
+    return tokens, {"prefill_ms": stat(p, 3), "decode_ms_per_token": stat(d, 4)}
+
+
+def add_adapters(llm, targets, r, alpha):
+    """Stand-in adapters from the test suite's LoraLinear (peft is not needed): A and B ~ N(0, 0.02), seed 11."""
+    try:
+        from tests import lora_reference as lo
+    except ImportError as e:
+        raise SystemExit("--lora takes its stand-in LoRA layer from tests/lora_reference.py: run from a checkout that has tests/ (%s)" % e)
+    return lo.inject_lora(llm, targets, r, alpha, 11, 0.02, 0.02)
 
 
 def main():
@@ -57,7 +87,11 @@ def main():
     ap.add_argument("--new", type=int, default=128)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--one-step", action="store_true")
+    ap.add_argument("--lora", default="", help="comma-separated projections that get a stand-in adapter, e.g. q_proj,v_proj")
+    ap.add_argument("--lora-r", type=int, default=8)
+    ap.add_argument("--lora-alpha", type=float, default=16)
     a = ap.parse_args()
+    targets = tuple(n for n in a.lora.split(",") if n)
     from walkgpt_amd.causal_lm import walkgptForCausalLM
     from walkgpt_amd.llama_hip import LlamaHipRunner
     dev = torch.device("cuda:0")
@@ -71,10 +105,34 @@ def main():
     stock = SimpleNamespace(llm=llm, eos_token_id=None, config=SimpleNamespace(pad_token_id=None), _hip_llm=None)
     with torch.no_grad():
         if a.one_step:
+            if targets:
+                runner = LlamaHipRunner(add_adapters(llm, targets, a.lora_r, a.lora_alpha))
             runner.generate(emb, mask, 4)
             torch.cuda.synchronize()
             runner._graph[0].replay()
             torch.cuda.synchronize()
+            return
+        if targets:
+            res = {"layers": a.layers, "rows": a.rows, "l0": a.l0, "new": a.new, "runs": a.runs,
+                   "lora": {"targets": list(targets), "r": a.lora_r, "alpha": a.lora_alpha}}
+            hip = lambda r: (lambda: r.prefill(emb, mask), lambda: r.generate(emb, mask, a.new, graph=True))
+            plain_tokens, res["lora"]["hip_graph_plain"] = measure(*hip(runner), a.runs, a.new)
+            del runner
+            add_adapters(llm, targets, a.lora_r, a.lora_alpha)
+            runner = LlamaHipRunner(llm)
+            tok, res["lora"]["hip_graph_adapted"] = measure(*hip(runner), a.runs, a.new)
+            tok_s, res["lora"]["stock_adapted"] = measure(lambda: llm(inputs_embeds=emb, attention_mask=mask, use_cache=True, output_hidden_states=True),
+                                                          lambda: walkgptForCausalLM._generate(stock, emb, mask, a.new), a.runs, a.new)
+            for m in llm.modules():
+                if hasattr(m, "lora_A"):
+                    m.disable_adapters = True
+            _, res["lora"]["hip_graph_disabled"] = measure(*hip(runner), a.runs, a.new)
+            med = lambda k: res["lora"][k]["decode_ms_per_token"]["median"]
+            res["lora"]["adapted_vs_plain_decode"] = round(med("hip_graph_adapted") / med("hip_graph_plain"), 4)
+            res["lora"]["hip_graph_vs_stock_decode"] = round(med("stock_adapted") / med("hip_graph_adapted"), 3)
+            res["lora"]["tokens_agreeing_with_stock"] = round(float((tok == tok_s).float().mean()), 3)
+            res["lora"]["tokens_changed_by_the_adapters"] = round(float((tok != plain_tokens).float().mean()), 3)
+            print(json.dumps(res))
             return
         paths = {
             "stock": (lambda: llm(inputs_embeds=emb, attention_mask=mask, use_cache=True, output_hidden_states=True),
@@ -89,7 +147,7 @@ def main():
             tokens[name] = generate()[0]               # warm-up (and, for the graphed path, the capture)
             p, t = timed(prefill, a.runs), timed(generate, a.runs)
             res[name] = {"prefill_ms": round(p, 3), "generate_ms": round(t, 3), "decode_ms_per_token": round((t - p) / max(1, a.new - 1), 4)}
-        w = sum(t.numel() * 2 for lw in runner._layers() for t in lw if t.dim() == 2) + llm.lm_head.weight.numel() * 2
+        w = sum(t.numel() * 2 for lw in runner._layers() for t in lw[:9] if t.dim() == 2) + llm.lm_head.weight.numel() * 2
         d = res["hip_graph"]["decode_ms_per_token"] * 1e-3
         res["weight_bytes_per_token"] = w
         res["hip_graph_share_of_copy_rate"] = round(w / d / COPY_RATE, 4)

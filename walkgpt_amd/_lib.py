@@ -145,6 +145,10 @@ SIGNATURES = {
                                   c_float, c_void_p],
     "wg_llama_gemv_bf16": [c_void_p, c_long, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_float, c_void_p, c_long, c_void_p,
                            c_long, c_int, c_int, c_int, c_void_p],
+    "wg_llama_rope_cache_lora_bf16": [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_int, c_int, c_int,
+                                      c_int, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_int, c_void_p],
+    "wg_llama_gemv_lora_bf16": [c_void_p, c_long, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_float, c_void_p, c_long,
+                                c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_long, c_void_p],
     "wg_llama_silu_mul_bf16": [c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_void_p],
     "wg_llama_pick_token": [c_void_p, c_long, c_void_p, c_int, c_void_p, c_long, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                             c_int, c_int, c_int, c_void_p],

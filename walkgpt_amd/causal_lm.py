@@ -500,7 +500,9 @@ class walkgptForCausalLM(nn.Module):  # noqa: N801  (the reference's class name)
     def enable_hip_llm(self, on: bool = True):
         """Opt-in: `_generate` (so `generate` and `evaluate`) runs the language model through the HIP LLaMA path of llama_hip.py -- a GEMM
         prefill and a graph-captured KV-cache decode step -- instead of one transformers forward per token.  Raises with
-        LlamaHipRunner.supports' reason when the model does not qualify (GQA, head_dim != 128, unmerged LoRA, ...).  model_forward and
+        LlamaHipRunner.supports' reason when the model does not qualify (GQA, head_dim != 128, a LoRA adapter on o_proj, ...).  Unmerged PEFT
+        LoRA adapters on q_proj, k_proj and v_proj qualify and are computed from the modules' own tensors; PEFT replaces the Linears inside
+        `self.llm` in place, so calling this on the PEFT-wrapped model (which forwards the attribute) switches the inner model.  model_forward and
         training never go through it; `enable_hip_llm(False)` drops the runner and its cache."""
         if not on:
             self._hip_llm = None

@@ -67,6 +67,11 @@ extern "C" int wg_rmsnorm_rows_bf16(const void* x, long ldx, const void* w, void
 //   out[i] = x[i] cos[i] - x[i + 64] sin[i],   out[i + 64] = x[i + 64] cos[i] + x[i] sin[i]      (fp32, one rounding)
 // q -> q_out [rows L, H]; rotated k and plain v -> the cache slot of position past_len + j.  A position outside [0, cap) writes no cache
 // slot (and reads the table's last row).
+// LoRA form (wg_llama_rope_cache_lora_bf16): the up-projection of unmerged adapters rides in here.  Before the rotation (for v: before
+// the copy) the adapted ones of q, k, v become, in fp32,  x[n] + s * sum_j B[n][j] t[tok][seg * rank + j]  (j ascending; B [H, rank]
+// bf16, its row rank / 8 16-byte loads; t fp32 [rows L, 3 rank], the down-projections the q | k | v GEMV left):
+//   q = bf16(rope(bf16(W_q xh) + s B_q t_q)), the same for k;  v = bf16(bf16(W_v xh) + s B_v t_v).
+// An unadapted v stays a copy and an unadapted q / k takes the arithmetic above.
 struct RopeArgs {
     const bf16* qkv; long ldqkv;
     const float* cos; const float* sin; int max_pos;
@@ -85,7 +90,67 @@ __device__ __forceinline__ void wg_rope8(const bf16x8 lo, const bf16x8 hi, const
     }
 }
 
-__global__ __launch_bounds__(256) void wg_llama_rope_cache_kernel(RopeArgs a) {
+struct RopeLoraArgs : RopeArgs {
+    const float* t; long ldt;
+    const bf16* b[3]; float s[3];
+    int rank;
+};
+
+// d[0 .. 7] / d[8 .. 15] = s * B[col + e] . t / s * B[col + 64 + e] . t, the adapter's term of this thread's 16 elements of projection `seg`
+// (j ascending).  The 16 rows of B are loaded together (16 bytes each per 8 columns of B) and the t slice once per thread.
+__device__ __forceinline__ void wg_lora_up16(const RopeLoraArgs& a, int seg, long tok, int col, float* d) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) d[e] = 0.f;
+    const bf16* b = a.b[seg] + (long)col * a.rank;
+    const float* t = a.t + tok * a.ldt + seg * a.rank;
+    for (int j = 0; j < a.rank; j += 8) {
+        bf16x8 bv[16];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) bv[e] = *(const bf16x8*)(b + (long)((e & 7) + (e >> 3) * 64) * a.rank + j);
+        const f32x4 t0 = *(const f32x4*)(t + j), t1 = *(const f32x4*)(t + j + 4);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) d[e] += (float)bv[e][u] * t0[u];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) d[e] += (float)bv[e][4 + u] * t1[u];
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 16; ++e) d[e] *= a.s[seg];
+}
+
+// The LoRA form's rotation: the operations are spelled out as the plain kernel's wg_rope8 compiles (one product, one fma each, in this
+// pairing), so a projection without an adapter -- or with B = 0 -- gives the plain kernel's bits.  That rests on how the compiler contracts
+// a * c - b * s in wg_rope8; what pins it are the GPU tests (tests/test_gpu_lora.py: all B null against the plain entry point, B = 0
+// against the plain model): if a compiler pairs wg_rope8 differently, they fail and this function follows it.
+__device__ __forceinline__ void wg_rope8f(const float* lo, const float* hi, const float* c, const float* s, bf16x8& olo, bf16x8& ohi) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        olo[e] = (bf16)__builtin_fmaf(lo[e], c[e], -(hi[e] * s[e]));
+        ohi[e] = (bf16)__builtin_fmaf(hi[e], c[e], lo[e] * s[e]);
+    }
+}
+
+// q or k of the LoRA form: lo / hi are this thread's two 8-element pieces of the projection, d is wg_lora_up16's, added where the projection has an adapter
+__device__ __forceinline__ void wg_rope8_lora(const bf16x8 lo, const bf16x8 hi, const float* d, bool adapted, const float* c, const float* s,
+                                              bf16x8& olo, bf16x8& ohi) {
+    float fl[8], fh[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { fl[e] = (float)lo[e]; fh[e] = (float)hi[e]; }
+    if (adapted) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { fl[e] += d[e]; fh[e] += d[8 + e]; }
+    }
+    wg_rope8f(fl, fh, c, s, olo, ohi);
+}
+
+// The LoRA form runs one thread per (token, head, 8 pairs, projection): blockIdx.y = 0 / 1 / 2 takes q / k / v alone.  The decode step has
+// rows * heads * 8 such threads per projection -- one workgroup -- so what the kernel costs there is its chain of dependent trips to
+// memory, not bytes; with a projection per workgroup the B rows, the t slice and the x pieces of a thread are all in flight at once and
+// the chain is as long as the plain kernel's.
+template <bool LORA>
+__global__ __launch_bounds__(256) void wg_llama_rope_cache_kernel(std::conditional_t<LORA, RopeLoraArgs, RopeArgs> a) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     const long total = (long)a.rows * a.L * a.heads * 8;
     if (i >= total) return;
@@ -106,6 +171,36 @@ __global__ __launch_bounds__(256) void wg_llama_rope_cache_kernel(RopeArgs a) {
     }
     const bf16* src = a.qkv + tok * a.ldqkv + head * WG_LLAMA_HD + c8 * 8;
     bf16x8 olo, ohi;
+    if constexpr (LORA) {
+        const int seg = blockIdx.y;
+        const bool adapted = a.b[seg] != nullptr;
+        const bf16x8 lo = *(const bf16x8*)(src + seg * H), hi = *(const bf16x8*)(src + seg * H + 64);
+        float d[16];
+        if (adapted) wg_lora_up16(a, seg, tok, head * WG_LLAMA_HD + c8 * 8, d);
+        if (seg == 0) {
+            wg_rope8_lora(lo, hi, d, adapted, c, s, olo, ohi);
+            bf16* qo = a.q_out + tok * a.ldq + head * WG_LLAMA_HD + c8 * 8;
+            *(bf16x8*)qo = olo;
+            *(bf16x8*)(qo + 64) = ohi;
+            return;
+        }
+        if (pos < 0 || pos >= a.cap) return;
+        const long slot = ((long)row * a.cap + pos) * H + head * WG_LLAMA_HD + c8 * 8;
+        if (seg == 1) {
+            wg_rope8_lora(lo, hi, d, adapted, c, s, olo, ohi);
+            *(bf16x8*)(a.kc + slot) = olo;
+            *(bf16x8*)(a.kc + slot + 64) = ohi;
+            return;
+        }
+        olo = lo; ohi = hi;
+        if (adapted) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { olo[e] = (bf16)((float)lo[e] + d[e]); ohi[e] = (bf16)((float)hi[e] + d[8 + e]); }
+        }
+        *(bf16x8*)(a.vc + slot) = olo;
+        *(bf16x8*)(a.vc + slot + 64) = ohi;
+        return;
+    }
     wg_rope8(*(const bf16x8*)src, *(const bf16x8*)(src + 64), c, s, olo, ohi);
     bf16* qo = a.q_out + tok * a.ldq + head * WG_LLAMA_HD + c8 * 8;
     *(bf16x8*)qo = olo;
@@ -119,20 +214,47 @@ __global__ __launch_bounds__(256) void wg_llama_rope_cache_kernel(RopeArgs a) {
     *(bf16x8*)(a.vc + slot + 64) = *(const bf16x8*)(src + 2 * H + 64);
 }
 
+static int wg_llama_rope_cache_check(const char* word, const void* qkv, long ldqkv, const float* cos_table, const float* sin_table, int max_pos,
+                                     const int* past_len, const void* q_out, long ldq, const void* k_cache, const void* v_cache, int rows, int L,
+                                     int heads, int cap) {
+    WG_REQUIRE(qkv && cos_table && sin_table && past_len && q_out && k_cache && v_cache, "%s: null operand", word);
+    WG_REQUIRE(rows > 0 && L > 0 && heads > 0 && max_pos > 0, "%s: bad shape", word);
+    WG_REQUIRE(cap > 0 && cap % 64 == 0, "%s: cache capacity %d must be a positive multiple of 64", word, cap);
+    const long H = (long)heads * WG_LLAMA_HD;
+    WG_REQUIRE(ldqkv >= 3 * H && ldq >= H && ldqkv % 8 == 0 && ldq % 8 == 0, "%s: leading dimensions too small or not multiples of 8", word);
+    WG_REQUIRE((((uintptr_t)qkv | (uintptr_t)cos_table | (uintptr_t)sin_table | (uintptr_t)q_out | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15) == 0,
+               "%s: misaligned operand", word);
+    return 0;
+}
+
 extern "C" int wg_llama_rope_cache_bf16(const void* qkv, long ldqkv, const float* cos_table, const float* sin_table, int max_pos,
                                         const int* past_len, void* q_out, long ldq, void* k_cache, void* v_cache, int rows, int L, int heads,
                                         int cap, void* stream) {
-    WG_REQUIRE(qkv && cos_table && sin_table && past_len && q_out && k_cache && v_cache, "llama_rope_cache: null operand");
-    WG_REQUIRE(rows > 0 && L > 0 && heads > 0 && max_pos > 0, "llama_rope_cache: bad shape");
-    WG_REQUIRE(cap > 0 && cap % 64 == 0, "llama_rope_cache: cache capacity %d must be a positive multiple of 64", cap);
-    const long H = (long)heads * WG_LLAMA_HD;
-    WG_REQUIRE(ldqkv >= 3 * H && ldq >= H && ldqkv % 8 == 0 && ldq % 8 == 0, "llama_rope_cache: leading dimensions too small or not multiples of 8");
-    WG_REQUIRE((((uintptr_t)qkv | (uintptr_t)cos_table | (uintptr_t)sin_table | (uintptr_t)q_out | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15) == 0,
-               "llama_rope_cache: misaligned operand");
+    if (const int rc = wg_llama_rope_cache_check("llama_rope_cache", qkv, ldqkv, cos_table, sin_table, max_pos, past_len, q_out, ldq, k_cache,
+                                                 v_cache, rows, L, heads, cap)) return rc;
     RopeArgs a{(const bf16*)qkv, ldqkv, cos_table, sin_table, max_pos, past_len, (bf16*)q_out, ldq, (bf16*)k_cache, (bf16*)v_cache, rows, L, heads, cap};
     const long total = (long)rows * L * heads * 8;
-    hipLaunchKernelGGL(wg_llama_rope_cache_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(wg_llama_rope_cache_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
     return wg_check_launch("wg_llama_rope_cache_bf16");
+}
+
+extern "C" int wg_llama_rope_cache_lora_bf16(const void* qkv, long ldqkv, const float* cos_table, const float* sin_table, int max_pos,
+                                             const int* past_len, void* q_out, long ldq, void* k_cache, void* v_cache, int rows, int L, int heads,
+                                             int cap, const float* t, long ldt, const void* b_q, const void* b_k, const void* b_v, float s_q,
+                                             float s_k, float s_v, int rank, void* stream) {
+    if (const int rc = wg_llama_rope_cache_check("llama_rope_cache_lora", qkv, ldqkv, cos_table, sin_table, max_pos, past_len, q_out, ldq, k_cache,
+                                                 v_cache, rows, L, heads, cap)) return rc;
+    WG_REQUIRE(rank >= 8 && rank <= 64 && rank % 8 == 0, "llama_rope_cache_lora: rank %d must be a multiple of 8, at most 64", rank);
+    if (b_q || b_k || b_v) {
+        WG_REQUIRE(t, "llama_rope_cache_lora: null operand (t, with an adapter given)");
+        WG_REQUIRE(ldt >= 3L * rank && ldt % 4 == 0, "llama_rope_cache_lora: ldt %ld too small for [rows L, 3 rank] (or not a multiple of 4)", ldt);
+        WG_REQUIRE((((uintptr_t)t | (uintptr_t)b_q | (uintptr_t)b_k | (uintptr_t)b_v) & 15) == 0, "llama_rope_cache_lora: misaligned B / t");
+    }
+    RopeLoraArgs a{{(const bf16*)qkv, ldqkv, cos_table, sin_table, max_pos, past_len, (bf16*)q_out, ldq, (bf16*)k_cache, (bf16*)v_cache, rows, L, heads,
+                    cap}, t, ldt, {(const bf16*)b_q, (const bf16*)b_k, (const bf16*)b_v}, {s_q, s_k, s_v}, rank};
+    const long total = (long)rows * L * heads * 8;
+    hipLaunchKernelGGL(wg_llama_rope_cache_kernel<true>, dim3((unsigned)((total + 255) / 256), 3), dim3(256), 0, (hipStream_t)stream, a);
+    return wg_check_launch("wg_llama_rope_cache_lora_bf16");
 }
 
 // ---- c. prefill attention -----------------------------------------------------------------------------------------------------------
@@ -407,6 +529,9 @@ extern "C" int wg_llama_attn_decode_bf16(const void* q, long ldq, const void* k_
 //   residual   out = res + acc (res may be out)
 //   pair       out[n] = silu(W_0[n] . xh) * (W_1[n] . xh)
 //   out_f32    fp32 output (the logits)
+//   lora       (wg_llama_gemv_lora_bf16) the rows of up to three adapter down-projections A_i [rank, K], A_i belonging to segment i, are
+//              further weight rows of the same launch, after the last W row and in segment order: t[m][i * rank + j] = A_i[j] . xh[m],
+//              fp32, not rounded (t [M, 3 rank]; the column block of an absent adapter is not written).  They take no residual.
 struct GemvArgs {
     const bf16* x; long ldx;
     const bf16* w[3]; int n[3];
@@ -416,9 +541,28 @@ struct GemvArgs {
     void* out; long ldo;
     int out_f32;
 };
+struct GemvLoraArgs : GemvArgs {
+    const bf16* la[3]; int rank;
+    float* t; long ldt;
+};
 
-template <int M, bool PAIR>
-__global__ __launch_bounds__(256) void wg_llama_gemv_kernel(GemvArgs a) {
+// LoRA row j (0 .. adapters * rank - 1, present adapters in segment order) -> its segment; j becomes the row inside that adapter
+__device__ __forceinline__ int wg_lora_row_segment(const GemvLoraArgs& a, int& j) {
+    int sgm = 0;
+    if (!a.la[0] || j >= a.rank) {
+        if (a.la[0]) j -= a.rank;
+        sgm = 1;
+        if (!a.la[1] || j >= a.rank) {
+            if (a.la[1]) j -= a.rank;
+            sgm = 2;
+        }
+    }
+    return sgm;
+}
+
+template <int M, bool PAIR, bool LORA = false>
+__global__ __launch_bounds__(256) void wg_llama_gemv_kernel(std::conditional_t<LORA, GemvLoraArgs, GemvArgs> a) {
+    static_assert(!(PAIR && LORA), "pair mode takes no adapters");
     constexpr int R = 4;                    // weight rows in flight per wave
     constexpr int RO = PAIR ? 2 : 4;        // output columns per wave
     __shared__ float red[4][8];
@@ -448,7 +592,9 @@ __global__ __launch_bounds__(256) void wg_llama_gemv_kernel(GemvArgs a) {
 #pragma unroll
         for (int m = 0; m < M; ++m) rstd[m] = 1.0f / sqrtf(((red[0][m] + red[1][m]) + (red[2][m] + red[3][m])) / (float)K + a.eps);
     }
-    const int ntot = PAIR ? a.n[0] : a.n[0] + a.n[1] + a.n[2];
+    const int nw = PAIR ? a.n[0] : a.n[0] + a.n[1] + a.n[2];      // output columns of W; ntot: those plus the adapter rows
+    int ntot = nw;
+    if constexpr (LORA) ntot += ((a.la[0] != nullptr) + (a.la[1] != nullptr) + (a.la[2] != nullptr)) * a.rank;
     const int n0 = (blockIdx.x * 4 + wave) * RO;
     if (n0 >= ntot) return;                 // (after the only barrier)
     const bf16* wp[R];
@@ -459,9 +605,20 @@ __global__ __launch_bounds__(256) void wg_llama_gemv_kernel(GemvArgs a) {
             wp[r] = a.w[r >> 1] + (long)n * K;
         } else {
             int n = n0 + r < ntot ? n0 + r : ntot - 1;
-            int sgm = 0;
-            if (n >= a.n[0]) { n -= a.n[0]; sgm = 1; if (n >= a.n[1]) { n -= a.n[1]; sgm = 2; } }
-            wp[r] = a.w[sgm] + (long)n * K;
+            bool lora_row = false;
+            if constexpr (LORA) {
+                if (n >= nw) {
+                    int j = n - nw;
+                    const int sgm = wg_lora_row_segment(a, j);
+                    wp[r] = a.la[sgm] + (long)j * K;
+                    lora_row = true;
+                }
+            }
+            if (!lora_row) {
+                int sgm = 0;
+                if (n >= a.n[0]) { n -= a.n[0]; sgm = 1; if (n >= a.n[1]) { n -= a.n[1]; sgm = 2; } }
+                wp[r] = a.w[sgm] + (long)n * K;
+            }
         }
     }
     float acc[R][M];
@@ -507,6 +664,15 @@ __global__ __launch_bounds__(256) void wg_llama_gemv_kernel(GemvArgs a) {
     for (int c = 0; c < RO; ++c) {
         const int n = n0 + c;
         if (n >= ntot) break;
+        if constexpr (LORA) {
+            if (n >= nw) {
+                int j = n - nw;
+                const int sgm = wg_lora_row_segment(a, j);
+#pragma unroll
+                for (int m = 0; m < M; ++m) a.t[(long)m * a.ldt + sgm * a.rank + j] = acc[c][m];
+                continue;
+            }
+        }
 #pragma unroll
         for (int m = 0; m < M; ++m) {
             float v;
@@ -536,18 +702,29 @@ template <bool PAIR> static void wg_llama_gemv_launch(const GemvArgs& a, int M, 
     }
 }
 
+template <int M> static void wg_llama_gemv_lora_launch_m(const GemvLoraArgs& a, unsigned blocks, hipStream_t st) {
+    hipLaunchKernelGGL((wg_llama_gemv_kernel<M, false, true>), dim3(blocks), dim3(256), 0, st, a);
+}
+
+static int wg_llama_gemv_check(const char* word, const void* x, long ldx, const void* w0, int n0, const void* w1, int n1, const void* w2, int n2,
+                               int K, const void* gamma, const void* residual, long ldr, const void* out, long ldo, int pair, int M) {
+    WG_REQUIRE(x && w0 && out, "%s: null operand", word);
+    WG_REQUIRE(M >= 1 && M <= 8, "%s: M = %d rows (1 .. 8)", word, M);
+    WG_REQUIRE(K > 0 && K % 128 == 0, "%s: K = %d must be a positive multiple of 128", word, K);
+    WG_REQUIRE(n0 >= 1 && n1 >= 0 && n2 >= 0 && (w1 || n1 == 0) && (w2 || n2 == 0) && (n1 > 0 || n2 == 0), "%s: bad weight segments", word);
+    WG_REQUIRE(!pair || (w1 && n1 == n0 && n2 == 0), "%s: pair mode takes two segments of equal N", word);
+    const long ntot = pair ? n0 : (long)n0 + n1 + n2;
+    WG_REQUIRE(ntot < (1L << 30), "%s: too many output columns", word);
+    WG_REQUIRE(ldx >= K && ldx % 8 == 0 && ldo >= ntot && (!residual || ldr >= ntot), "%s: leading dimensions too small (or ldx not a multiple of 8)", word);
+    WG_REQUIRE((((uintptr_t)x | (uintptr_t)w0 | (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)gamma) & 15) == 0, "%s: misaligned operand", word);
+    return 0;
+}
+
 extern "C" int wg_llama_gemv_bf16(const void* x, long ldx, const void* w0, int n0, const void* w1, int n1, const void* w2, int n2, int K,
                                   const void* gamma, float eps, const void* residual, long ldr, void* out, long ldo, int out_f32, int pair, int M,
                                   void* stream) {
-    WG_REQUIRE(x && w0 && out, "llama_gemv: null operand");
-    WG_REQUIRE(M >= 1 && M <= 8, "llama_gemv: M = %d rows (1 .. 8)", M);
-    WG_REQUIRE(K > 0 && K % 128 == 0, "llama_gemv: K = %d must be a positive multiple of 128", K);
-    WG_REQUIRE(n0 >= 1 && n1 >= 0 && n2 >= 0 && (w1 || n1 == 0) && (w2 || n2 == 0) && (n1 > 0 || n2 == 0), "llama_gemv: bad weight segments");
-    WG_REQUIRE(!pair || (w1 && n1 == n0 && n2 == 0), "llama_gemv: pair mode takes two segments of equal N");
+    if (const int rc = wg_llama_gemv_check("llama_gemv", x, ldx, w0, n0, w1, n1, w2, n2, K, gamma, residual, ldr, out, ldo, pair, M)) return rc;
     const long ntot = pair ? n0 : (long)n0 + n1 + n2;
-    WG_REQUIRE(ntot < (1L << 30), "llama_gemv: too many output columns");
-    WG_REQUIRE(ldx >= K && ldx % 8 == 0 && ldo >= ntot && (!residual || ldr >= ntot), "llama_gemv: leading dimensions too small (or ldx not a multiple of 8)");
-    WG_REQUIRE((((uintptr_t)x | (uintptr_t)w0 | (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)gamma) & 15) == 0, "llama_gemv: misaligned operand");
     GemvArgs a{(const bf16*)x, ldx, {(const bf16*)w0, (const bf16*)w1, (const bf16*)w2}, {n0, n1, n2}, K, (const bf16*)gamma, eps,
                (const bf16*)residual, ldr, out, ldo, out_f32};
     const int per_block = 4 * (pair ? 2 : 4);
@@ -555,6 +732,36 @@ extern "C" int wg_llama_gemv_bf16(const void* x, long ldx, const void* w0, int n
     if (pair) wg_llama_gemv_launch<true>(a, M, blocks, (hipStream_t)stream);
     else wg_llama_gemv_launch<false>(a, M, blocks, (hipStream_t)stream);
     return wg_check_launch("wg_llama_gemv_bf16");
+}
+
+extern "C" int wg_llama_gemv_lora_bf16(const void* x, long ldx, const void* w0, int n0, const void* w1, int n1, const void* w2, int n2, int K,
+                                       const void* gamma, float eps, const void* residual, long ldr, void* out, long ldo, int out_f32, int pair,
+                                       int M, const void* a0, const void* a1, const void* a2, int rank, float* t, long ldt, void* stream) {
+    if (const int rc = wg_llama_gemv_check("llama_gemv_lora", x, ldx, w0, n0, w1, n1, w2, n2, K, gamma, residual, ldr, out, ldo, pair, M)) return rc;
+    WG_REQUIRE(rank >= 8 && rank <= 64 && rank % 8 == 0, "llama_gemv_lora: rank %d must be a multiple of 8, at most 64", rank);
+    WG_REQUIRE(!pair, "llama_gemv_lora: pair mode takes no adapters");
+    WG_REQUIRE((!a1 || n1 > 0) && (!a2 || n2 > 0), "llama_gemv_lora: an adapter on a segment that is not there");
+    if (a0 || a1 || a2) {
+        WG_REQUIRE(t, "llama_gemv_lora: null operand (t, with an adapter given)");
+        WG_REQUIRE(ldt >= 3L * rank && ldt % 4 == 0, "llama_gemv_lora: ldt %ld too small for [M, 3 rank] (or not a multiple of 4)", ldt);
+        WG_REQUIRE((((uintptr_t)a0 | (uintptr_t)a1 | (uintptr_t)a2 | (uintptr_t)t) & 15) == 0, "llama_gemv_lora: misaligned A / t");
+    }
+    GemvLoraArgs a{{(const bf16*)x, ldx, {(const bf16*)w0, (const bf16*)w1, (const bf16*)w2}, {n0, n1, n2}, K, (const bf16*)gamma, eps,
+                    (const bf16*)residual, ldr, out, ldo, out_f32}, {(const bf16*)a0, (const bf16*)a1, (const bf16*)a2}, rank, t, ldt};
+    const long ntot = (long)n0 + n1 + n2 + (long)((a0 != nullptr) + (a1 != nullptr) + (a2 != nullptr)) * rank;
+    const unsigned blocks = (unsigned)((ntot + 15) / 16);
+    const hipStream_t st = (hipStream_t)stream;
+    switch (M) {
+        case 1: wg_llama_gemv_lora_launch_m<1>(a, blocks, st); break;
+        case 2: wg_llama_gemv_lora_launch_m<2>(a, blocks, st); break;
+        case 3: wg_llama_gemv_lora_launch_m<3>(a, blocks, st); break;
+        case 4: wg_llama_gemv_lora_launch_m<4>(a, blocks, st); break;
+        case 5: wg_llama_gemv_lora_launch_m<5>(a, blocks, st); break;
+        case 6: wg_llama_gemv_lora_launch_m<6>(a, blocks, st); break;
+        case 7: wg_llama_gemv_lora_launch_m<7>(a, blocks, st); break;
+        default: wg_llama_gemv_lora_launch_m<8>(a, blocks, st); break;
+    }
+    return wg_check_launch("wg_llama_gemv_lora_bf16");
 }
 
 // ---- SiLU(gate) * up on a [M, 2 I] buffer (gate | up), the prefill's MLP middle ------------------------------------------------------

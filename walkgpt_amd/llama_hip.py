@@ -2,6 +2,12 @@
 step of weight-streaming GEMVs, captured once into a HIP graph and replayed per token.  Opt-in (walkgptForCausalLM.enable_hip_llm); the
 runner reads the `transformers` LlamaForCausalLM's own weight tensors -- nothing is packed or copied.
 
+Unmerged LoRA adapters on q_proj, k_proj and / or v_proj (PEFT's lora.Linear, recognised by its attributes: peft itself is not needed) are
+computed as W x + scaling * B (A x) without a further launch in the decode step: the rows of A are further weight rows of the q | k | v
+GEMV (t = A xh, fp32, into a [rows, 3 r] buffer) and the rope + cache kernel adds scaling * B t to the q, k, v elements it reads anyway.
+The runner reads the modules' own base_layer.weight, lora_A[name].weight and lora_B[name].weight.  A merged or disabled layer counts
+as its base_layer; a model without active adapters takes the plain entry points.
+
 Decode step, per layer: gemv (RMSNorm -> q | k | v), rope + cache write, decode attention (+ its combine), gemv (o_proj + residual), gemv (RMSNorm ->
 SwiGLU), gemv (down_proj + residual); then the final RMSNorm into the hidden-state buffer, the lm_head gemv and the device-side token pick.  After
 the pick a step needs nothing from the host: the host only looks at the tokens every `sync_every` steps to see whether every row has finished.
@@ -44,6 +50,39 @@ def trimmed_length(tokens, eos, max_new_tokens):
         if bool(hit.any(1).all()):
             return int(hit.int().argmax(1).max()) + 1
     return max_new_tokens if steps >= max_new_tokens else None
+
+
+LORA_TARGETS = ("q_proj", "k_proj", "v_proj")
+
+
+def _is_lora(m):
+    """PEFT's lora.Linear by its attributes: a Linear at base_layer, ModuleDicts lora_A / lora_B from adapter name to a Linear."""
+    return isinstance(getattr(m, "base_layer", None), nn.Linear) and isinstance(getattr(m, "lora_A", None), nn.ModuleDict) \
+        and isinstance(getattr(m, "lora_B", None), nn.ModuleDict)
+
+
+def _active_adapters(m):
+    """The adapter names the layer's own forward would apply: none when it is merged or disabled."""
+    if getattr(m, "merged", False) or getattr(m, "disable_adapters", False):
+        return []
+    names = getattr(m, "active_adapters", None) or []
+    names = [names] if isinstance(names, str) else list(names)
+    return [a for a in names if a in m.lora_A and a in m.lora_B]
+
+
+def _base(m):
+    return m.base_layer if _is_lora(m) else m
+
+
+def _adapter(m):
+    """-> None for a plain (or merged / disabled) projection, else (name, A [r, in], B [out, r], scaling) of its one active adapter."""
+    if not _is_lora(m):
+        return None
+    names = _active_adapters(m)
+    if not names:
+        return None
+    a = names[0]
+    return a, m.lora_A[a].weight, m.lora_B[a].weight, float(m.scaling[a])
 
 
 class _Buffers:
@@ -90,7 +129,20 @@ class LlamaHipRunner:
             tensors += [layer.input_layernorm.weight, layer.post_attention_layernorm.weight]
             linears += [("layers.%d.self_attn.%s" % (i, n), getattr(layer.self_attn, n)) for n in ("q_proj", "k_proj", "v_proj", "o_proj")]
             linears += [("layers.%d.mlp.%s" % (i, n), getattr(layer.mlp, n)) for n in ("gate_proj", "up_proj", "down_proj")]
+        adapters, first_rank = [], None
         for name, m in linears:
+            if _is_lora(m) and type(m.base_layer) is nn.Linear:
+                why = LlamaHipRunner._lora_refusal(name, m)
+                if why:
+                    return False, why
+                ad = _adapter(m)
+                if ad is not None:
+                    r = ad[1].shape[0]
+                    if first_rank is not None and r != first_rank[1]:
+                        return False, "%s: LoRA rank %d differs from the rank %d of %s: one rank per model" % (name, r, first_rank[1], first_rank[0])
+                    first_rank = first_rank or (name, r)
+                    adapters += [(name, ad[1]), (name, ad[2])]
+                m = m.base_layer
             if type(m) is not nn.Linear:
                 return False, "%s is a %s, not a plain nn.Linear: merge the adapters first" % (name, type(m).__name__)
             if m.bias is not None:
@@ -101,30 +153,89 @@ class LlamaHipRunner:
                 return False, "weights must be bf16 on a GPU (found %s on %s)" % (str(t.dtype).replace("torch.", ""), t.device)
             if not t.is_contiguous():
                 return False, "weights must be contiguous"
+        for name, t in adapters:
+            if t.dtype != BF16 or not t.is_cuda or not t.is_contiguous():
+                return False, "%s: adapter weights must be contiguous bf16 on a GPU (found %s on %s)" % (name, str(t.dtype).replace("torch.", ""), t.device)
         return True, ""
+
+    @staticmethod
+    def _lora_refusal(name, m):
+        """Why the LoRA layer `m` (PEFT's lora.Linear by its attributes) is not covered, or None.  Structure only: no dtype, no device."""
+        names = _active_adapters(m)
+        if not names:
+            return None                          # merged or disabled: its own forward is base_layer's
+        if name.rsplit(".", 1)[-1] not in LORA_TARGETS:
+            return "LoRA on %s: only q_proj, k_proj and v_proj adapters are built; merge the others" % name
+        if len(names) > 1:
+            return "%s: %d active adapters (%s): one active adapter per layer is built" % (name, len(names), ", ".join(names))
+        a = names[0]
+        if (getattr(m, "use_dora", None) or {}).get(a, False):
+            return "%s: adapter %r uses DoRA: not built" % (name, a)
+        A, B = m.lora_A[a], m.lora_B[a]
+        if not isinstance(A, nn.Linear) or not isinstance(B, nn.Linear):
+            return "%s: lora_A / lora_B of adapter %r are not nn.Linear" % (name, a)
+        if B.bias is not None or A.bias is not None:
+            return "%s: lora_%s of adapter %r has a bias: not built" % (name, "B" if B.bias is not None else "A", a)
+        r = A.weight.shape[0]
+        if A.weight.shape != (r, m.base_layer.in_features) or B.weight.shape != (m.base_layer.out_features, r):
+            return "%s: adapter %r has shapes %s / %s that do not fit the base layer" % (name, a, tuple(A.weight.shape), tuple(B.weight.shape))
+        if r % 8 or not 8 <= r <= 64:
+            return "%s: LoRA rank %d: the kernels take multiples of 8 up to 64" % (name, r)
+        if a not in getattr(m, "scaling", {}):
+            return "%s: adapter %r has no scaling" % (name, a)
+        drop = getattr(m, "lora_dropout", None)
+        drop = drop[a] if drop is not None and a in drop else None
+        if m.training and isinstance(drop, nn.Dropout) and drop.p > 0:
+            return "%s: LoRA dropout p = %g is live in training mode: call eval() first" % (name, drop.p)
+        return None
 
     # -- weights -----------------------------------------------------------------------------------------------------------------------------
     def _layers(self):
+        """Per layer the nine base weights, then the adapters: None (the plain path), or per q, k, v projection None or (name, A, B, scaling)."""
         out = []
         for layer in self.llm.model.layers:
             a, m = layer.self_attn, layer.mlp
-            out.append((layer.input_layernorm.weight, a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, a.o_proj.weight,
-                        layer.post_attention_layernorm.weight, m.gate_proj.weight, m.up_proj.weight, m.down_proj.weight))
+            lora = tuple(_adapter(getattr(a, n)) for n in LORA_TARGETS)
+            out.append((layer.input_layernorm.weight, _base(a.q_proj).weight, _base(a.k_proj).weight, _base(a.v_proj).weight, _base(a.o_proj).weight,
+                        layer.post_attention_layernorm.weight, _base(m.gate_proj).weight, _base(m.up_proj).weight, _base(m.down_proj).weight,
+                        lora if any(ad is not None for ad in lora) else None))
         return out
 
+    def _head(self):
+        return _base(self.llm.lm_head).weight
+
+    def _rank(self):
+        """The adapters' common rank (supports() has seen to it that there is one), 0 without adapters."""
+        for lw in self._layers():
+            for ad in lw[9] or ():
+                if ad is not None:
+                    return int(ad[1].shape[0])
+        return 0
+
     def _weight_key(self):
-        ts = [t for lw in self._layers() for t in lw] + [self.llm.model.norm.weight, self.llm.lm_head.weight, self.llm.get_input_embeddings().weight]
-        return tuple((t.data_ptr(), t._version, t.dtype) for t in ts)
+        """What a captured decode step has baked in: data_ptr, _version and dtype of every weight, and per adapted projection the adapter's
+        name, the same of its A and B, and its scaling.  A merged or disabled adapter is absent from it, so switching one changes the key."""
+        ident = lambda t: (t.data_ptr(), t._version, t.dtype)
+        key = [ident(t) for t in (self.llm.model.norm.weight, self._head(), self.llm.get_input_embeddings().weight)]
+        for lw in self._layers():
+            key += [ident(t) for t in lw[:9]]
+            if lw[9] is not None:
+                key.append(tuple(None if ad is None else (ad[0], ident(ad[1]), ident(ad[2]), ad[3]) for ad in lw[9]))
+        return tuple(key)
 
     # -- buffers of one (rows, cap) signature ------------------------------------------------------------------------------------------------
     def _buffers(self, rows, cap, dev):
         b = self._buf
         if b is not None and (b.rows, b.cap, b.dev) == (rows, cap, dev):
+            r = self._rank()
+            if r and (b.t is None or b.t.shape[1] != 3 * r):
+                b.t = torch.zeros(rows, 3 * r, device=dev, dtype=torch.float32)
+                self._graph = None               # a captured step holds the old buffer
             return b
         self._buf = self._graph = None           # the old signature's cache and graph go first: two caches need not fit
         b = _Buffers()
         b.rows, b.cap, b.dev = rows, cap, dev
-        H, I, V = self.hidden, self.inter, self.llm.lm_head.weight.shape[0]
+        H, I, V = self.hidden, self.inter, self._head().shape[0]
         e = lambda *s, dtype=BF16: torch.empty(*s, device=dev, dtype=dtype)
         b.kv = [(e(rows, cap, H), e(rows, cap, H)) for _ in self.llm.model.layers]
         b.hs = e(rows, cap, H)
@@ -135,6 +246,8 @@ class LlamaHipRunner:
         b.tokens = torch.zeros(rows, cap, device=dev, dtype=torch.int64)
         b.x, b.qkv, b.q, b.attn, b.act = e(rows, H), e(rows, 3 * H), e(rows, H), e(rows, H), e(rows, I)
         b.x.zero_()
+        r = self._rank()
+        b.t = torch.zeros(rows, 3 * r, device=dev, dtype=torch.float32) if r else None      # the adapters' down-projections of a decode step
         b.logits = e(rows, V, dtype=torch.float32)
         b.ws = ops.llama_attn_decode_workspace(rows, self.heads, dev)
         cos, sin = rope_table(self.llm.config, cap)
@@ -146,7 +259,10 @@ class LlamaHipRunner:
     @torch.no_grad()
     def prefill(self, inputs_embeds, attention_mask, cap=None, all_logits=False):
         """-> (post-model.norm hidden states [rows, L0, H] bf16, fp32 logits [rows, V] of the last position or [rows, L0, V] of all).  Fills the KV
-        cache of the (rows, cap) buffers; all_logits runs the lm_head 8 rows at a time (a checking aid, not a fast path)."""
+        cache of the (rows, cap) buffers; all_logits runs the lm_head 8 rows at a time (a checking aid, not a fast path).
+        Adapters: their down-projection t = xn A^T goes through the decode GEMV with the roles swapped -- 8 rows of A as its `x`, the
+        rows * L0 rows of xn as its weight, fp32 output t^T, one launch per 8 rows of A (_prefill_lora_t) -- and the rope + cache kernel
+        adds the up-projection.  xn is here the bf16-rounded output of the RMSNorm kernel; the decode step's GEMV takes it unrounded."""
         rows, L0, H = inputs_embeds.shape
         if rows > MAX_ROWS:
             raise NotImplementedError("LlamaHipRunner: %d rows (the decode GEMV takes at most %d)" % (rows, MAX_ROWS))
@@ -161,18 +277,25 @@ class LlamaHipRunner:
         qkv = torch.empty(M, 3 * H, device=h.device, dtype=BF16)
         q = torch.empty(M, H, device=h.device, dtype=BF16)
         gu = torch.empty(M, 2 * I, device=h.device, dtype=BF16)
-        for (ln1, wq, wk, wv, wo, ln2, wg, wu, wd), (kc, vc) in zip(self._layers(), b.kv):
+        r = self._rank()
+        t = torch.zeros(M, 3 * r, device=h.device, dtype=torch.float32) if r else None      # the adapters' down-projections, reused by every layer
+        tt = torch.empty(r, M, device=h.device, dtype=torch.float32) if r else None
+        for (ln1, wq, wk, wv, wo, ln2, wg, wu, wd, lora), (kc, vc) in zip(self._layers(), b.kv):
             xn = ops.rmsnorm(h, ln1, self.eps)
             for i, w in enumerate((wq, wk, wv)):
                 ops.linear(xn, w, out=qkv[:, i * H:(i + 1) * H])
-            ops.llama_rope_cache(qkv, b.cos, b.sin, b.zero, q, kc, vc, rows, L0, heads)
+            if lora is None:
+                ops.llama_rope_cache(qkv, b.cos, b.sin, b.zero, q, kc, vc, rows, L0, heads)
+            else:
+                ops.llama_rope_cache(qkv, b.cos, b.sin, b.zero, q, kc, vc, rows, L0, heads, t=self._prefill_lora_t(xn, lora, t, tt),
+                                     lora_b=[ad and ad[2] for ad in lora], lora_scale=[ad[3] if ad else 0.0 for ad in lora])
             att = ops.llama_attn_prefill(q, kc, vc, b.mask, b.zero, L0, heads, self.scale)
             h = ops.linear(att, wo, residual=h)
             xn = ops.rmsnorm(h, ln2, self.eps)
             ops.linear(xn, wg, out=gu[:, :I])
             ops.linear(xn, wu, out=gu[:, I:])
             h = ops.linear(ops.llama_silu_mul(gu), wd, residual=h)
-        norm_w, head_w = self.llm.model.norm.weight, self.llm.lm_head.weight
+        norm_w, head_w = self.llm.model.norm.weight, self._head()
         h3 = h.view(rows, L0, H)
         for r in range(rows):
             ops.rmsnorm(h3[r], norm_w, self.eps, out=b.hs[r, :L0])
@@ -185,19 +308,38 @@ class LlamaHipRunner:
             ops.llama_gemv(h[m0:m0 + MAX_ROWS], [head_w], gamma=norm_w, eps=self.eps, out=logits[m0:m0 + MAX_ROWS], out_f32=True)
         return hidden, logits.view(rows, L0, -1)
 
+    @staticmethod
+    def _prefill_lora_t(xn, lora, t, tt):
+        """Fills t [M, 3 r] fp32, column block i = xn A_i^T for the adapted ones of q, k, v (the others are not read): the GEMV kernel with
+        xn [M, K] as its weight and 8 rows of A_i as its input gives 8 rows of t^T in tt [r, M]; the transposed copy into t is the only step
+        outside the kernels."""
+        r = tt.shape[0]
+        for i, ad in enumerate(lora):
+            if ad is None:
+                continue
+            for j in range(0, r, MAX_ROWS):
+                ops.llama_gemv(ad[1][j:j + MAX_ROWS], [xn], out=tt[j:j + MAX_ROWS], out_f32=True)
+            t[:, i * r:(i + 1) * r] = tt.t()
+        return t
+
     # -- one decode step: a linear chain of launches on the current stream, no allocation, no host read ---------------------------------------
     def _decode_step(self, b, eos, pad):
         past, heads = b.state[0:1], self.heads
-        for (ln1, wq, wk, wv, wo, ln2, wg, wu, wd), (kc, vc) in zip(self._layers(), b.kv):
-            ops.llama_gemv(b.x, [wq, wk, wv], gamma=ln1, eps=self.eps, out=b.qkv)
-            ops.llama_rope_cache(b.qkv, b.cos, b.sin, past, b.q, kc, vc, b.rows, 1, heads)
+        for (ln1, wq, wk, wv, wo, ln2, wg, wu, wd, lora), (kc, vc) in zip(self._layers(), b.kv):
+            if lora is None:
+                ops.llama_gemv(b.x, [wq, wk, wv], gamma=ln1, eps=self.eps, out=b.qkv)
+                ops.llama_rope_cache(b.qkv, b.cos, b.sin, past, b.q, kc, vc, b.rows, 1, heads)
+            else:                                # the adapters ride in the same two launches
+                ops.llama_gemv(b.x, [wq, wk, wv], gamma=ln1, eps=self.eps, out=b.qkv, lora_a=[ad and ad[1] for ad in lora], t_out=b.t)
+                ops.llama_rope_cache(b.qkv, b.cos, b.sin, past, b.q, kc, vc, b.rows, 1, heads, t=b.t, lora_b=[ad and ad[2] for ad in lora],
+                                     lora_scale=[ad[3] if ad else 0.0 for ad in lora])
             ops.llama_attn_decode(b.q, kc, vc, b.mask, past, heads, self.scale, workspace=b.ws, out=b.attn)
             ops.llama_gemv(b.attn, [wo], residual=b.x, out=b.x)
             ops.llama_gemv(b.x, [wg, wu], gamma=ln2, eps=self.eps, out=b.act, pair=True)
             ops.llama_gemv(b.act, [wd], residual=b.x, out=b.x)
         norm_w = self.llm.model.norm.weight
         ops.rmsnorm(b.x, norm_w, self.eps, out=b.hs, slot=past)           # the hidden state of the token at position past_len
-        ops.llama_gemv(b.x, [self.llm.lm_head.weight], gamma=norm_w, eps=self.eps, out=b.logits, out_f32=True)
+        ops.llama_gemv(b.x, [self._head()], gamma=norm_w, eps=self.eps, out=b.logits, out_f32=True)
         self._pick(b, eos, pad)
 
     def _pick(self, b, eos, pad):

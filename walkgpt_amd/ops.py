@@ -1204,17 +1204,45 @@ def rmsnorm(x, weight, eps, out=None, slot=None, slot_add=0):
     return out
 
 
-def llama_rope_cache(qkv, cos, sin, past_len, q_out, k_cache, v_cache, rows, L, heads):
-    """qkv [rows * L, 3H] -> rotated q in q_out [rows * L, H], rotated k and v into k_cache / v_cache [rows, cap, H] at positions past_len + j."""
+def _lora_rank(mats, rank_axis, other, t):
+    """The common rank of the adapter matrices given (None = no adapter on that segment); with none given, t's third of a row, else 8."""
+    ranks = {int(m.shape[rank_axis]) for m in mats if m is not None}
+    assert len(ranks) <= 1, "one LoRA rank per call"
+    for m in mats:
+        assert m is None or (m.dtype == _BF16 and m.dim() == 2 and m.is_contiguous() and m.shape[1 - rank_axis] == other)
+    if ranks:
+        return ranks.pop()
+    return int(t.shape[1]) // 3 if t is not None else 8
+
+
+def llama_rope_cache(qkv, cos, sin, past_len, q_out, k_cache, v_cache, rows, L, heads, t=None, lora_b=None, lora_scale=None):
+    """qkv [rows * L, 3H] -> rotated q in q_out [rows * L, H], rotated k and v into k_cache / v_cache [rows, cap, H] at positions past_len + j.
+    lora_b = (B_q, B_k, B_v), each [H, r] bf16 or None, lora_scale their three scalings and t fp32 [rows * L, 3 r] (llama_gemv's t_out): the
+    adapted ones become x + scale * B t before the rotation (wg_llama_rope_cache_lora_bf16); lora_b None is the plain entry point."""
     _need_gpu(qkv, cos, sin, past_len, q_out, k_cache, v_cache)
     H = heads * 128
     assert qkv.dtype == _BF16 and qkv.shape == (rows * L, 3 * H) and q_out.shape == (rows * L, H) and q_out.dtype == _BF16
     assert cos.dtype == torch.float32 and cos.is_contiguous() and cos.shape[1] == 64 and sin.shape == cos.shape and sin.is_contiguous()
     assert past_len.dtype == torch.int32
     assert k_cache.is_contiguous() and k_cache.dtype == _BF16 and k_cache.shape[0] == rows and k_cache.shape[2] == H and v_cache.shape == k_cache.shape
-    _lib.check(_lib.lib().wg_llama_rope_cache_bf16(qkv.data_ptr(), qkv.stride(0), cos.data_ptr(), sin.data_ptr(), cos.shape[0], past_len.data_ptr(),
-                                                   q_out.data_ptr(), q_out.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), rows, L, heads,
-                                                   k_cache.shape[1], _stream()), "wg_llama_rope_cache_bf16")
+    if lora_b is None:
+        assert t is None and lora_scale is None
+        _lib.check(_lib.lib().wg_llama_rope_cache_bf16(qkv.data_ptr(), qkv.stride(0), cos.data_ptr(), sin.data_ptr(), cos.shape[0], past_len.data_ptr(),
+                                                       q_out.data_ptr(), q_out.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), rows, L, heads,
+                                                       k_cache.shape[1], _stream()), "wg_llama_rope_cache_bf16")
+        return q_out
+    lora_b = list(lora_b)
+    assert len(lora_b) == 3
+    _need_gpu(t, *lora_b)
+    rank = _lora_rank(lora_b, 1, H, t)
+    scale = [0.0 if b is None else float(sc) for b, sc in zip(lora_b, lora_scale or (0.0, 0.0, 0.0))]
+    assert t is None or (t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.shape == (rows * L, 3 * rank))
+    assert t is not None or all(b is None for b in lora_b)
+    _lib.check(_lib.lib().wg_llama_rope_cache_lora_bf16(qkv.data_ptr(), qkv.stride(0), cos.data_ptr(), sin.data_ptr(), cos.shape[0], past_len.data_ptr(),
+                                                        q_out.data_ptr(), q_out.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), rows, L, heads,
+                                                        k_cache.shape[1], _ptr(t), 0 if t is None else t.stride(0), _ptr(lora_b[0]), _ptr(lora_b[1]),
+                                                        _ptr(lora_b[2]), scale[0], scale[1], scale[2], rank, _stream()),
+               "wg_llama_rope_cache_lora_bf16")
     return q_out
 
 
@@ -1257,9 +1285,11 @@ def llama_attn_decode(q, k_cache, v_cache, mask, past_len, heads, scale, workspa
     return out
 
 
-def llama_gemv(x, weights, gamma=None, eps=0.0, residual=None, out=None, out_f32=False, pair=False):
+def llama_gemv(x, weights, gamma=None, eps=0.0, residual=None, out=None, out_f32=False, pair=False, lora_a=None, t_out=None):
     """x [M <= 8, K] against one to three weights [N_i, K] whose outputs sit side by side in `out` [M, sum N_i] (pair: silu(W_0 x) * (W_1 x),
-    [M, N_0]).  gamma: RMSNorm prologue; residual: added before the rounding (may be `out`)."""
+    [M, N_0]).  gamma: RMSNorm prologue; residual: added before the rounding (may be `out`).
+    lora_a: per weight an adapter down-projection [r, K] bf16 or None; their products with the same (normalised) input go, fp32, into
+    t_out [M, 3 r], column block i for weight i, in the same launch (wg_llama_gemv_lora_bf16).  lora_a None is the plain entry point."""
     weights = list(weights)
     _need_gpu(x, gamma, residual, out, *weights)
     assert x.dtype == _BF16 and 1 <= len(weights) <= 3
@@ -1275,9 +1305,22 @@ def llama_gemv(x, weights, gamma=None, eps=0.0, residual=None, out=None, out_f32
     assert gamma is None or (gamma.dtype == _BF16 and gamma.numel() == K and gamma.is_contiguous())
     assert residual is None or residual.shape[-1] == N
     ptrs = [w.data_ptr() for w in weights] + [0] * (3 - len(weights))
-    _lib.check(_lib.lib().wg_llama_gemv_bf16(x.data_ptr(), ldx, ptrs[0], ns[0], ptrs[1], ns[1], ptrs[2], ns[2], K, _ptr(gamma), float(eps),
-                                             _ptr(residual), _residual_ld(residual), out.data_ptr(), ldo, 1 if out_f32 else 0, 1 if pair else 0, M,
-                                             _stream()), "wg_llama_gemv_bf16")
+    if lora_a is None:
+        assert t_out is None
+        _lib.check(_lib.lib().wg_llama_gemv_bf16(x.data_ptr(), ldx, ptrs[0], ns[0], ptrs[1], ns[1], ptrs[2], ns[2], K, _ptr(gamma), float(eps),
+                                                 _ptr(residual), _residual_ld(residual), out.data_ptr(), ldo, 1 if out_f32 else 0, 1 if pair else 0, M,
+                                                 _stream()), "wg_llama_gemv_bf16")
+        return out
+    lora_a = list(lora_a) + [None] * (3 - len(lora_a))
+    assert len(lora_a) == 3
+    _need_gpu(t_out, *lora_a)
+    rank = _lora_rank(lora_a, 0, K, t_out)
+    assert t_out is None or (t_out.dtype == torch.float32 and t_out.dim() == 2 and t_out.stride(1) == 1 and t_out.shape == (M, 3 * rank))
+    assert t_out is not None or all(a is None for a in lora_a)
+    _lib.check(_lib.lib().wg_llama_gemv_lora_bf16(x.data_ptr(), ldx, ptrs[0], ns[0], ptrs[1], ns[1], ptrs[2], ns[2], K, _ptr(gamma), float(eps),
+                                                  _ptr(residual), _residual_ld(residual), out.data_ptr(), ldo, 1 if out_f32 else 0,
+                                                  1 if pair else 0, M, _ptr(lora_a[0]), _ptr(lora_a[1]), _ptr(lora_a[2]), rank, _ptr(t_out),
+                                                  0 if t_out is None else t_out.stride(0), _stream()), "wg_llama_gemv_lora_bf16")
     return out
 
 
