@@ -246,7 +246,11 @@ int wg_upscale_mask_bf16(const void* x, long ldx, const void* w1, const void* b1
  * Both take an optional `combine` table of 5 pointers {attention partials, out_proj weight [256,128], out_proj bias, LayerNorm gamma, beta}:
  *   when given, x holds the tokens BEFORE the COMBINE stage and the launch runs that stage itself (one launch less on the chain):
  *   the MLP kernel writes the tokens after norm2 to x_out (a buffer other than x); the heads kernel applies the final attention's
- *   out_proj + norm_final_attn to the token row each workgroup needs. */
+ *   out_proj + norm_final_attn to the token row each workgroup needs.
+ * The arithmetic of every stage above, of wg_dec_i2t_rows_bf16 and of wg_upscale_mask_bf16 is stated in tests/decoder_reference.py: float64
+ *   references in plain torch (tokens_reference, attn_partial_reference / merge_partials, mlp_partial_reference, heads_reference,
+ *   i2t_rows_reference, upscale_reference), the fp32 emulation of what the kernels keep (activations staged as a bf16 hi + lo pair, fp32
+ *   accumulation, bf16 only where this ABI says bf16) and the per-row tolerance tests/test_gpu_decoder_kernels.py holds each kernel to. */
 /* Every weight MATRIX the four wg_dec_* token kernels take (not biases / LayerNorm vectors) is in fragment order, made once per checkpoint:
  *   wg_tile_weight_bf16: W [N][K] bf16 (row stride ld) -> T[ceil(N/16)][K/32][64][8],  T[nb][ks][lane][j] = W[16 nb + lane%16][32 ks + 8 (lane/16) + j]
  *   (rows >= N zero): the 1 KiB a wave loads per MFMA step is contiguous (3x the per-CU streaming rate of the row-major pattern).
