@@ -532,8 +532,8 @@ int wg_nce_tail_bwd_dev_f32(const void* z, const void* vp, const float* sim, con
 int wg_nce_tail_bwd_f32(const void* z, const void* vp, const float* sim, const int* own_row, const float* lse_m, float g, void* dz, void* dvp,
                         float* dsim, int M, int rows, int N, int D, float temperature, int exclude_same_row, void* stream);
 
-/* ---- the LLaMA generate path (csrc/llama.hip; host: walkgpt_amd/llama_hip.py).  head_dim 128, bf16 data, fp32 arithmetic, fixed summation
- * order.  KV cache: K and V [rows, cap, H] bf16 per layer (H = heads * 128, cap % 64 == 0); key mask uint8 [rows, cap], 1 = attend.
+/* ---- the LLaMA generate path (csrc/llama.hip; host: walkgpt_amd/llama_hip.py).  head_dim 128, bf16 data (the projection weights of the
+ * decode step optionally as e4m3 bytes: wg_llama_*_e4m3 below), fp32 arithmetic, fixed summation order.  KV cache: K and V [rows, cap, H] bf16 per layer (H = heads * 128, cap % 64 == 0); key mask uint8 [rows, cap], 1 = attend.
  * Device state int32: past_len -- for rope_cache / attn_prefill the number of tokens already cached (token j of the call sits at position
  * past_len + j), for attn_decode / pick_token the position of the current token; every index derived from it is clamped inside the kernels.
  *
@@ -580,6 +580,30 @@ int wg_llama_gemv_bf16(const void* x, long ldx, const void* w0, int n0, const vo
 int wg_llama_gemv_lora_bf16(const void* x, long ldx, const void* w0, int n0, const void* w1, int n1, const void* w2, int n2, int K, const void* gamma,
                             float eps, const void* residual, long ldr, void* out, long ldo, int out_f32, int pair, int M, const void* a0,
                             const void* a1, const void* a2, int rank, float* t, long ldt, void* stream);
+/* ---- e4m3 weight-only decode (W8A16): projection weights as OCP e4m3 bytes with one power-of-two fp32 scale per output row, bf16
+ * activations, fp32 arithmetic.  For W [N, K] bf16 and row n with amax = max_k |W[n][k]|: e[n] = the smallest integer with
+ * amax <= 448 * 2^e (on the bf16 bits: amax = m * 2^x, m in [0.5, 1): e = x - 9 for m <= 0.875, else x - 8), clamped to [-126, 127], 0 for
+ * an all-zero row; scale[n] = 2^e[n]; q[n][k] = W[n][k] / scale[n] rounded to e4m3fn, nearest-even.  W' = q * scale is exactly a bf16
+ * value.  Rows with a non-finite weight are outside the contract.  These entry points only add symbols: wg_version() stays 300.
+ *
+ * wg_llama_quantize_weight_e4m3: w [N, K] bf16 contiguous -> q [N, K] bytes, scale [N]; bit-exact, K % 16 == 0, w and q 16-byte aligned.
+ * wg_llama_dequantize_weight_bf16: q, scale -> w = W' [N, K] bf16, exact (a scale is read by its exponent field alone). */
+int wg_llama_quantize_weight_e4m3(const void* w, void* q, float* scale, int N, int K, void* stream);
+int wg_llama_dequantize_weight_bf16(const void* q, const float* scale, void* w, int N, int K, void* stream);
+/* wg_llama_gemv_e4m3: wg_llama_gemv_bf16 with byte weights: w_i [N_i, K] e4m3 bytes (contiguous, read once by 16-byte loads), s_i [N_i] their
+ *   row scales; out[m][n] = scale[n] * sum_k xh[m][k] q[n][k], the scale applied to the sum (exact) before SiLU (pair) and the residual.
+ *   Everything else -- M <= 8, K % 128 == 0, segments, gamma / eps, residual, pair, out_f32 -- as wg_llama_gemv_bf16.  Checked before any
+ *   pointer is read, each < 0 with "llama_gemv_e4m3" in wg_last_error(): everything wg_llama_gemv_bf16 checks; the scale of a segment
+ *   that is there NULL or not 4-byte aligned. */
+int wg_llama_gemv_e4m3(const void* x, long ldx, const void* w0, const float* s0, int n0, const void* w1, const float* s1, int n1, const void* w2,
+                       const float* s2, int n2, int K, const void* gamma, float eps, const void* residual, long ldr, void* out, long ldo,
+                       int out_f32, int pair, int M, void* stream);
+/* wg_llama_gemv_lora_e4m3: wg_llama_gemv_lora_bf16 with byte weights; the adapter rows a_i stay bf16 and t fp32, not rounded.  out is what
+ *   wg_llama_gemv_e4m3 gives, bit for bit.  Checks: those of wg_llama_gemv_e4m3 and of wg_llama_gemv_lora_bf16, with "llama_gemv_lora_e4m3". */
+int wg_llama_gemv_lora_e4m3(const void* x, long ldx, const void* w0, const float* s0, int n0, const void* w1, const float* s1, int n1,
+                            const void* w2, const float* s2, int n2, int K, const void* gamma, float eps, const void* residual, long ldr,
+                            void* out, long ldo, int out_f32, int pair, int M, const void* a0, const void* a1, const void* a2, int rank, float* t,
+                            long ldt, void* stream);
 /* wg_llama_silu_mul_bf16: out[m][i] = silu(gate_up[m][i]) * gate_up[m][I + i], I % 8 == 0 */
 int wg_llama_silu_mul_bf16(const void* gate_up, long ldgu, void* out, long ldo, int M, int I, void* stream);
 /* wg_llama_pick_token: per row (rows <= 8) the argmax of fp32 logits [rows, V] (lowest index on a tie); a finished row emits pad and

@@ -7,13 +7,18 @@ time per token, (generation - prefill) / (new - 1).  Also: the weight bytes a de
 measured on an MI355X.  Prints one JSON line; results belong in profiles/llm_generate.md.
 
     python tools/bench_llm.py [--layers 32] [--rows 1] [--l0 320] [--new 128] [--runs 5] [--one-step] [--lora q_proj,v_proj --lora-r 8 --lora-alpha 16]
+                              [--weights e4m3]
 --one-step: no timing; after a warm generation, replay ONE graphed decode step (for `rocprofv3 --kernel-trace --stats -- python tools/bench_llm.py
 --one-step`, whose per-kernel table then holds that step on top of the warm-up).
 --lora: unmerged LoRA adapters.  The plain model is measured first (graphed HIP path), then stand-in adapters (tests/lora_reference.py's
 LoraLinear, the attributes of PEFT's layer; random A and random non-zero B) go onto the named projections of every layer and the same process
 measures the graphed HIP path and the stock path on the adapted model, and last the graphed HIP path with every adapter disabled (the plain
 path again, as a control for drift inside the process).  "lora" in the JSON line: prefill ms and decode ms/token of the four, each with the
-lowest and highest of its runs.  The stand-in layer comes from tests/lora_reference.py, so --lora needs the checkout's tests/ directory.  With --one-step the replayed step is the adapted model's."""
+lowest and highest of its runs.  The stand-in layer comes from tests/lora_reference.py, so --lora needs the checkout's tests/ directory.  With --one-step the replayed step is the adapted model's.
+--weights e4m3: the e4m3 weight-only decode (LlamaHipRunner(llm, weights="e4m3")) against the bf16 path in one process: the bf16 graphed path is
+measured first, then the e4m3 graphed path on the same model (with --lora: on the same adapted model).  "weights" in the JSON line: prefill ms
+and decode ms/token of the two (median, lowest, highest of the runs), the bytes a decode step streams in each mode and their rate, the time the
+store took to build, and the share of the generated tokens on which the two modes agree.  With --one-step the replayed step is the e4m3 one."""
 import argparse
 import json
 import os
@@ -90,6 +95,7 @@ def main():
     ap.add_argument("--lora", default="", help="comma-separated projections that get a stand-in adapter, e.g. q_proj,v_proj")
     ap.add_argument("--lora-r", type=int, default=8)
     ap.add_argument("--lora-alpha", type=float, default=16)
+    ap.add_argument("--weights", default="bf16", choices=("bf16", "e4m3"), help="e4m3: measure the e4m3 weight-only decode against the bf16 path")
     a = ap.parse_args()
     targets = tuple(n for n in a.lora.split(",") if n)
     from walkgpt_amd.causal_lm import walkgptForCausalLM
@@ -104,6 +110,44 @@ def main():
     # _generate as the model runs it, without the grounding modules around it: `self` only has to carry what _generate reads
     stock = SimpleNamespace(llm=llm, eos_token_id=None, config=SimpleNamespace(pad_token_id=None), _hip_llm=None)
     with torch.no_grad():
+        if a.weights == "e4m3":
+            del runner
+            if targets:
+                add_adapters(llm, targets, a.lora_r, a.lora_alpha)
+            if a.one_step:
+                runner = LlamaHipRunner(llm, weights="e4m3")
+                runner.generate(emb, mask, 4)
+                torch.cuda.synchronize()
+                runner._graph[0].replay()
+                torch.cuda.synchronize()
+                return
+            res = {"layers": a.layers, "rows": a.rows, "l0": a.l0, "new": a.new, "runs": a.runs, "weights": {}}
+            if targets:
+                res["lora"] = {"targets": list(targets), "r": a.lora_r, "alpha": a.lora_alpha}
+            hip = lambda r: (lambda: r.prefill(emb, mask), lambda: r.generate(emb, mask, a.new, graph=True))
+            w = res["weights"]
+            runner = LlamaHipRunner(llm)
+            tok16, w["bf16"] = measure(*hip(runner), a.runs, a.new)
+            proj = [t for lw in runner._layers() for t in lw[1:5] + lw[6:9]]
+            head = llm.lm_head.weight.numel() * 2
+            del runner                                 # its KV cache and graph go before the next runner's come
+            runner = LlamaHipRunner(llm, weights="e4m3")
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            runner._refresh_store()
+            torch.cuda.synchronize()
+            w["store_build_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
+            tok8, w["e4m3"] = measure(*hip(runner), a.runs, a.new)
+            w["store_bytes"] = sum(q.numel() + s.numel() * 4 for q, s in (runner._store[t] for t in proj))
+            med = lambda k, what: w[k][what]["median"]
+            for k, b in (("bf16", sum(t.numel() * 2 for t in proj) + head), ("e4m3", w["store_bytes"] + head)):
+                w[k]["weight_bytes_per_token"] = b
+                w[k]["share_of_copy_rate"] = round(b / (med(k, "decode_ms_per_token") * 1e-3) / COPY_RATE, 4)
+            w["e4m3_vs_bf16_decode"] = round(med("e4m3", "decode_ms_per_token") / med("bf16", "decode_ms_per_token"), 4)
+            w["e4m3_vs_bf16_prefill"] = round(med("e4m3", "prefill_ms") / med("bf16", "prefill_ms"), 4)
+            w["tokens_agreeing_with_bf16"] = round(float((tok8 == tok16).float().mean()), 3)
+            print(json.dumps(res))
+            return
         if a.one_step:
             if targets:
                 runner = LlamaHipRunner(add_adapters(llm, targets, a.lora_r, a.lora_alpha))

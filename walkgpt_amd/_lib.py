@@ -149,6 +149,13 @@ SIGNATURES = {
                                       c_int, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_int, c_void_p],
     "wg_llama_gemv_lora_bf16": [c_void_p, c_long, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_float, c_void_p, c_long,
                                 c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_long, c_void_p],
+    "wg_llama_quantize_weight_e4m3": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
+    "wg_llama_dequantize_weight_bf16": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
+    "wg_llama_gemv_e4m3": [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                           c_float, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int, c_void_p],
+    "wg_llama_gemv_lora_e4m3": [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                c_float, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                c_long, c_void_p],
     "wg_llama_silu_mul_bf16": [c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_void_p],
     "wg_llama_pick_token": [c_void_p, c_long, c_void_p, c_int, c_void_p, c_long, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                             c_int, c_int, c_int, c_void_p],

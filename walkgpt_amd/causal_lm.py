@@ -497,21 +497,25 @@ class walkgptForCausalLM(nn.Module):  # noqa: N801  (the reference's class name)
     # -- generation (walkgpt.py:629-639, evaluation_walkgpt.py:569-577) ---------------------------------------------------------------
     _hip_llm = None           # the LlamaHipRunner while enable_hip_llm() is on; None (the default): the stock transformers path below
 
-    def enable_hip_llm(self, on: bool = True):
+    def enable_hip_llm(self, on: bool = True, weights: str = "bf16"):
         """Opt-in: `_generate` (so `generate` and `evaluate`) runs the language model through the HIP LLaMA path of llama_hip.py -- a GEMM
         prefill and a graph-captured KV-cache decode step -- instead of one transformers forward per token.  Raises with
         LlamaHipRunner.supports' reason when the model does not qualify (GQA, head_dim != 128, a LoRA adapter on o_proj, ...).  Unmerged PEFT
         LoRA adapters on q_proj, k_proj and v_proj qualify and are computed from the modules' own tensors; PEFT replaces the Linears inside
         `self.llm` in place, so calling this on the PEFT-wrapped model (which forwards the attribute) switches the inner model.  model_forward and
-        training never go through it; `enable_hip_llm(False)` drops the runner and its cache."""
+        training never go through it; `enable_hip_llm(False)` drops the runner and its cache.
+        weights="e4m3": the decode step reads the layers' projection weights as e4m3 bytes with a power-of-two scale per output row (W8A16;
+        llama_hip.py's docstring has the format and the memory cost: one byte per projection weight, 6.5 GB at 7B, beside the model's own
+        bf16 tensors, which stay as they are).  Every call builds a new runner, so switching the mode or switching off drops the byte store."""
+        from .llama_hip import LlamaHipRunner, check_weight_mode
+        check_weight_mode(weights)
         if not on:
             self._hip_llm = None
             return self
-        from .llama_hip import LlamaHipRunner
         ok, why = LlamaHipRunner.supports(self.llm)
         if not ok:
             raise ValueError("enable_hip_llm: " + why)
-        self._hip_llm = LlamaHipRunner(self.llm)
+        self._hip_llm = LlamaHipRunner(self.llm, weights=weights)
         return self
 
     @property

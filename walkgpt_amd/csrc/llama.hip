@@ -1,5 +1,6 @@
 // The LLaMA generate path (walkgpt_amd/llama_hip.py): RMSNorm, RoPE + KV-cache write, causal prefill attention, split-key decode
-// attention, the decode GEMV and the device-side token pick.  bf16 data, fp32 arithmetic, no float atomics, every sum in a fixed
+// attention, the decode GEMV -- on bf16 weights and, for the e4m3 weight-only mode, on e4m3 bytes with a scale per row (section e2, with
+// its quantiser and dequantiser) -- and the device-side token pick.  bf16 data, fp32 arithmetic, no float atomics, every sum in a fixed
 // order (a run repeats bit for bit).  No launch function allocates or synchronises: all of them run inside a graph capture.
 //
 // Device state of a generation (int32, read by the kernels so that a captured decode step bakes in no length):
@@ -762,6 +763,449 @@ extern "C" int wg_llama_gemv_lora_bf16(const void* x, long ldx, const void* w0, 
         default: wg_llama_gemv_lora_launch_m<8>(a, blocks, st); break;
     }
     return wg_check_launch("wg_llama_gemv_lora_bf16");
+}
+
+// ---- e2. e4m3 weight-only decode (W8A16) ----------------------------------------------------------------------------------------------
+// The projection weights as OCP e4m3 bytes with one power-of-two scale per output row; activations bf16, arithmetic fp32.
+// Format, for W [N, K] bf16 and row n with amax = max_k |W[n][k]|:  e[n] = the smallest integer with amax <= 448 * 2^e, clamped to
+// [-126, 127] (an all-zero row: e = 0);  scale[n] = 2^e[n] (fp32);  q[n][k] = W[n][k] / scale[n] rounded to e4m3, nearest-even.
+// W' = q * scale is exactly a bf16 value (4 significant bits times a power of two), so the quantised model is an ordinary model with
+// the weights W', and the prefill runs the bf16 GEMMs on W'.  e is found on the bf16 bits: amax = m * 2^x with m in [0.5, 1) gives
+// e = x - 9 for m <= 0.875 and x - 8 above.  The quantiser and the dequantiser work on the bit fields alone (no float multiply sees
+// a subnormal, whatever the kernel's denormal mode), which is what makes them exact for every finite input; a non-finite weight is
+// outside the contract (it gives some byte, never an access outside the buffers).
+
+// |v| = (1 + mm / 128) * 2^(eb - 127) for the non-zero bf16 magnitude bits `a` (15 bits): a normal value as it stands, a subnormal normalised
+__device__ __forceinline__ void wg_bf16_fields(unsigned a, int& eb, unsigned& mm) {
+    eb = (int)(a >> 7);
+    mm = a & 0x7fu;
+    if (eb == 0) {                          // subnormal: mm * 2^-133, mm in 1 .. 127
+        const int s = __builtin_clz(mm) - 24;       // shifts that bring the leading one to bit 7
+        mm = (mm << s) & 0x7fu;
+        eb = 1 - s;
+    }
+}
+
+// the e4m3 byte of bf16 bits `h` divided by 2^e, round to nearest even
+__device__ __forceinline__ unsigned wg_e4m3_of_bf16_scaled(unsigned h, int e) {
+    const unsigned sign = (h >> 8) & 0x80u, a = h & 0x7fffu;
+    if (a == 0) return sign;
+    int eb;
+    unsigned mm;
+    wg_bf16_fields(a, eb, mm);
+    int ue = eb - 127 - e;                  // the quotient is sig * 2^(ue - 7), sig in 128 .. 255
+    const unsigned sig = 128u | mm;
+    if (ue >= -6) {                         // an e4m3 normal: 4 of the 8 significant bits stay
+        unsigned q = sig >> 4;
+        const unsigned rem = sig & 15u;
+        if (rem > 8u || (rem == 8u && (q & 1u))) ++q;
+        if (q == 16u) { q = 8u; ++ue; }
+        const unsigned byte = ((unsigned)(ue + 7) << 3) | (q & 7u);
+        return sign | (byte > 0x7eu ? 0x7eu : byte);          // (not reached by a row's own scale: nothing exceeds 448)
+    }
+    const int sh = -(ue + 2);               // an e4m3 subnormal, in units of 2^-9: sig >> sh, sh >= 5
+    if (sh > 9) return sign;                // below half a unit
+    const unsigned q = sig >> sh, rem = sig & ((1u << sh) - 1u), half = 1u << (sh - 1);
+    return sign | (q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u));      // (8 units are the smallest normal, 0x08)
+}
+
+// the bf16 bits of e4m3 byte `b` times 2^e: exact for every (q, scale) the quantiser leaves
+__device__ __forceinline__ unsigned wg_bf16_of_e4m3_scaled(unsigned b, int e) {
+    const unsigned sign = (b & 0x80u) << 8;
+    int ef = (int)((b >> 3) & 15u);
+    unsigned f = b & 7u;
+    if (ef == 0) {
+        if (f == 0) return sign;
+        const int s = __builtin_clz(f) - 28;        // shifts that bring the leading one to bit 3
+        f = (f << s) & 7u;
+        ef = 1 - s;
+    }
+    const int eb = ef - 7 + e + 127;
+    const unsigned m7 = f << 4;
+    if (eb >= 255) return sign | 0x7f80u;
+    if (eb >= 1) return sign | ((unsigned)eb << 7) | m7;
+    const int sh = 1 - eb;                  // a bf16 subnormal: the bits that leave are zeros for a quantiser's (q, scale)
+    return sign | (sh > 8 ? 0u : ((128u | m7) >> sh));
+}
+
+// One 256-thread block per row; the row maximum is taken on the magnitude bits (integers: exact and the same in any order).
+__global__ __launch_bounds__(256) void wg_llama_quantize_e4m3_kernel(const unsigned short* w, unsigned char* q, float* scale, int K) {
+    __shared__ unsigned red[4];
+    const int tid = threadIdx.x;
+    const long row = blockIdx.x;
+    const unsigned short* wr = w + row * K;
+    unsigned amax = 0;
+    for (int k = tid * 16; k < K; k += 4096) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const u32x4 t = *(const u32x4*)(wr + k + 8 * h);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const unsigned lo = t[c] & 0x7fffu, hi = (t[c] >> 16) & 0x7fffu;
+                amax = amax > lo ? amax : lo;
+                amax = amax > hi ? amax : hi;
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const unsigned o = (unsigned)__shfl_xor((int)amax, s, 64);
+        amax = amax > o ? amax : o;
+    }
+    if ((tid & 63) == 0) red[tid >> 6] = amax;
+    __syncthreads();
+    amax = red[0] > red[1] ? red[0] : red[1];
+    amax = amax > red[2] ? amax : red[2];
+    amax = amax > red[3] ? amax : red[3];
+    int e = 0;
+    if (amax != 0) {
+        int eb;
+        unsigned mm;
+        wg_bf16_fields(amax, eb, mm);
+        e = eb - 126 - (mm <= 96u ? 9 : 8);           // amax = m * 2^x: x = eb - 126, m = (1 + mm / 128) / 2 <= 0.875 is mm <= 96
+        e = wg_clampi(e, -126, 127);
+    }
+    if (tid == 0) scale[row] = __builtin_bit_cast(float, (unsigned)(e + 127) << 23);
+    unsigned char* qr = q + row * K;
+    for (int k = tid * 16; k < K; k += 4096) {
+        u32x4 o;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const u32x4 t = *(const u32x4*)(wr + k + 8 * h);
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                unsigned v = 0;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const unsigned d = t[2 * c + j];
+                    v |= (wg_e4m3_of_bf16_scaled(d & 0xffffu, e) | (wg_e4m3_of_bf16_scaled(d >> 16, e) << 8)) << (16 * j);
+                }
+                o[2 * h + c] = v;
+            }
+        }
+        *(u32x4*)(qr + k) = o;
+    }
+}
+
+extern "C" int wg_llama_quantize_weight_e4m3(const void* w, void* q, float* scale, int N, int K, void* stream) {
+    WG_REQUIRE(w && q && scale, "llama_quantize_weight_e4m3: null operand");
+    WG_REQUIRE(N > 0 && K > 0 && K % 16 == 0, "llama_quantize_weight_e4m3: bad shape (N %d, K %d; K must be a multiple of 16)", N, K);
+    WG_REQUIRE((((uintptr_t)w | (uintptr_t)q) & 15) == 0 && ((uintptr_t)scale & 3) == 0, "llama_quantize_weight_e4m3: misaligned operand");
+    hipLaunchKernelGGL(wg_llama_quantize_e4m3_kernel, dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)w,
+                       (unsigned char*)q, scale, K);
+    return wg_check_launch("wg_llama_quantize_weight_e4m3");
+}
+
+// One thread per 16 weights: W'[n][k] = q[n][k] * scale[n] as bf16, exact.  The scale's exponent field is all that is read of it.
+__global__ __launch_bounds__(256) void wg_llama_dequantize_bf16_kernel(const unsigned char* q, const float* scale, unsigned short* w, long total, int K) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long row = i / (K / 16);
+    const int e = (int)((__builtin_bit_cast(unsigned, scale[row]) >> 23) & 0xffu) - 127;
+    const u32x4 t = *(const u32x4*)(q + i * 16);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        u32x4 o;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const unsigned d = t[2 * h + (c >> 1)] >> (16 * (c & 1));
+            o[c] = wg_bf16_of_e4m3_scaled(d & 0xffu, e) | (wg_bf16_of_e4m3_scaled((d >> 8) & 0xffu, e) << 16);
+        }
+        *(u32x4*)(w + i * 16 + 8 * h) = o;
+    }
+}
+
+extern "C" int wg_llama_dequantize_weight_bf16(const void* q, const float* scale, void* w, int N, int K, void* stream) {
+    WG_REQUIRE(q && scale && w, "llama_dequantize_weight_bf16: null operand");
+    WG_REQUIRE(N > 0 && K > 0 && K % 16 == 0, "llama_dequantize_weight_bf16: bad shape (N %d, K %d; K must be a multiple of 16)", N, K);
+    WG_REQUIRE((((uintptr_t)w | (uintptr_t)q) & 15) == 0 && ((uintptr_t)scale & 3) == 0, "llama_dequantize_weight_bf16: misaligned operand");
+    const long total = (long)N * (K / 16);
+    WG_REQUIRE((total + 255) / 256 < (1L << 31), "llama_dequantize_weight_bf16: too many elements");
+    hipLaunchKernelGGL(wg_llama_dequantize_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned char*)q, scale, (unsigned short*)w, total, K);
+    return wg_check_launch("wg_llama_dequantize_weight_bf16");
+}
+
+// The decode GEMV on byte weights: out[m][n] = scale[n] * sum_k xh[m][k] q[n][k], wg_llama_gemv_bf16's contract otherwise (segments, norm,
+// residual, pair, out_f32).  A wave owns 4 weight rows as there; lane l takes the 16-byte pieces l, l + 64, ... of each row (16 weights a
+// load, a sweep of the wave covers 1024 of K: K = 128 keeps 8 lanes busy, K = 11008 ends in a sweep of 48), converts them with
+// v_cvt_pk_f32_fp8 (OCP on gfx950, exact) and adds its K / 64 products one after the other in element order, 8 elements of the 4 rows at a
+// time; the wave adds the lane sums by the same butterfly.  The scale multiplies the wave's sum -- a power of two, so exact -- before
+// SiLU and the residual.
+//   lora   (wg_llama_gemv_lora_e4m3) the adapter rows stay bf16 and take waves of their own, so a wave holds rows of one kind: the first
+//          waves of the launch (an adapter wave streams twice the bytes of a W wave, so it starts with the grid and not behind it;
+//          measured on the 7B q | k | v launch, first or last made no difference: 21.3 / 20.7 us).  They are summed as
+//          wg_llama_gemv_lora_bf16 sums them (8-element pieces) and leave as fp32 into t.
+struct GemvQArgs : GemvArgs {
+    const float* s[3];
+};
+struct GemvQLoraArgs : GemvQArgs {
+    const bf16* la[3]; int rank;
+    float* t; long ldt;
+};
+
+// xf[m][e] = the normalised input elements k .. k + 7 of the M rows
+template <int M, class A>
+__device__ __forceinline__ void wg_gemv_x8(const A& a, const float* rstd, int k, float (&xf)[M][8]) {
+    float g[8];
+    if (a.gamma) {
+        const bf16x8 t = *(const bf16x8*)(a.gamma + k);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) g[e] = (float)t[e];
+    }
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+        const bf16x8 t = *(const bf16x8*)(a.x + (long)m * a.ldx + k);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) xf[m][e] = a.gamma ? (float)t[e] * rstd[m] * g[e] : (float)t[e];
+    }
+}
+
+template <int M, bool PAIR, bool LORA = false>
+__global__ __launch_bounds__(256) void wg_llama_gemv_e4m3_kernel(std::conditional_t<LORA, GemvQLoraArgs, GemvQArgs> a) {
+    static_assert(!(PAIR && LORA), "pair mode takes no adapters");
+    constexpr int R = 4;
+    constexpr int RO = PAIR ? 2 : 4;
+    __shared__ float red[4][8];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int K = a.K;
+    float rstd[M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) rstd[m] = 1.f;
+    if (a.gamma) {
+        float ss[M];
+#pragma unroll
+        for (int m = 0; m < M; ++m) ss[m] = 0.f;
+        for (int k = tid * 8; k < K; k += 2048) {
+#pragma unroll
+            for (int m = 0; m < M; ++m) {
+                const bf16x8 t = *(const bf16x8*)(a.x + (long)m * a.ldx + k);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) ss[m] += (float)t[e] * (float)t[e];
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            const float t = wg_wave_sum(ss[m]);
+            if (lane == 0) red[wave][m] = t;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < M; ++m) rstd[m] = 1.0f / sqrtf(((red[0][m] + red[1][m]) + (red[2][m] + red[3][m])) / (float)K + a.eps);
+    }
+    const int nw = PAIR ? a.n[0] : a.n[0] + a.n[1] + a.n[2];
+    const int wi = blockIdx.x * 4 + wave;       // (every return is after the only barrier)
+    float acc[R][M];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int m = 0; m < M; ++m) acc[r][m] = 0.f;
+    int l_waves = 0;                            // the launch's first waves take the adapter rows
+    if constexpr (LORA) {
+        const int nl = ((a.la[0] != nullptr) + (a.la[1] != nullptr) + (a.la[2] != nullptr)) * a.rank;
+        l_waves = (nl + R - 1) / R;
+        if (wi < l_waves) {                     // a wave of adapter rows: bf16, wg_llama_gemv_kernel's loop
+            const int j0 = wi * R;
+            const bf16* wp[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                int j = j0 + r < nl ? j0 + r : nl - 1;
+                int sgm = 0;
+                if (!a.la[0] || j >= a.rank) {
+                    if (a.la[0]) j -= a.rank;
+                    sgm = 1;
+                    if (!a.la[1] || j >= a.rank) {
+                        if (a.la[1]) j -= a.rank;
+                        sgm = 2;
+                    }
+                }
+                wp[r] = a.la[sgm] + (long)j * K;
+            }
+#pragma unroll 2
+            for (int k = lane * 8; k < K; k += 512) {
+                u32x4 wv[R];
+#pragma unroll
+                for (int r = 0; r < R; ++r) wv[r] = __builtin_nontemporal_load((const u32x4*)(wp[r] + k));
+                float xf[M][8];
+                wg_gemv_x8<M>(a, rstd, k, xf);
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const bf16x8 wb = __builtin_bit_cast(bf16x8, wv[r]);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const float wf = (float)wb[e];
+#pragma unroll
+                        for (int m = 0; m < M; ++m) acc[r][m] += xf[m][e] * wf;
+                    }
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+#pragma unroll
+                for (int m = 0; m < M; ++m) acc[r][m] = wg_wave_sum(acc[r][m]);
+            if (lane != 0) return;
+#pragma unroll
+            for (int c = 0; c < R; ++c) {
+                int j = j0 + c;
+                if (j >= nl) break;
+                int sgm = 0;
+                if (!a.la[0] || j >= a.rank) {
+                    if (a.la[0]) j -= a.rank;
+                    sgm = 1;
+                    if (!a.la[1] || j >= a.rank) {
+                        if (a.la[1]) j -= a.rank;
+                        sgm = 2;
+                    }
+                }
+#pragma unroll
+                for (int m = 0; m < M; ++m) a.t[(long)m * a.ldt + sgm * a.rank + j] = acc[c][m];
+            }
+            return;
+        }
+    }
+    const int n0 = (wi - l_waves) * RO;
+    if (n0 >= nw) return;
+    const unsigned char* wp[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        if constexpr (PAIR) {
+            const int n = n0 + (r & 1) < nw ? n0 + (r & 1) : nw - 1;
+            wp[r] = (const unsigned char*)a.w[r >> 1] + (long)n * K;
+        } else {
+            int n = n0 + r < nw ? n0 + r : nw - 1;
+            int sgm = 0;
+            if (n >= a.n[0]) { n -= a.n[0]; sgm = 1; if (n >= a.n[1]) { n -= a.n[1]; sgm = 2; } }
+            wp[r] = (const unsigned char*)a.w[sgm] + (long)n * K;
+        }
+    }
+#pragma unroll 2
+    for (int k = lane * 16; k < K; k += 1024) {
+        u32x4 wv[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) wv[r] = __builtin_nontemporal_load((const u32x4*)(wp[r] + k));
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            float xf[M][8];
+            wg_gemv_x8<M>(a, rstd, k + 8 * h, xf);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    const int d = (int)wv[r][2 * h + c];
+                    const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8(d, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(d, true);
+                    const float wf[4] = {lo[0], lo[1], hi[0], hi[1]};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+#pragma unroll
+                        for (int m = 0; m < M; ++m) acc[r][m] += xf[m][4 * c + e] * wf[e];
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int m = 0; m < M; ++m) acc[r][m] = wg_wave_sum(acc[r][m]);
+    if (lane != 0) return;
+#pragma unroll
+    for (int c = 0; c < RO; ++c) {
+        const int n = n0 + c;
+        if (n >= nw) break;
+        float sc0, sc1 = 0.f;
+        if constexpr (PAIR) {
+            sc0 = a.s[0][n];
+            sc1 = a.s[1][n];
+        } else {
+            int j = n, sgm = 0;
+            if (j >= a.n[0]) { j -= a.n[0]; sgm = 1; if (j >= a.n[1]) { j -= a.n[1]; sgm = 2; } }
+            sc0 = a.s[sgm][j];
+        }
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            float v;
+            if constexpr (PAIR) {
+                const float gt = acc[c][m] * sc0, up = acc[2 + c][m] * sc1;
+                v = gt / (1.0f + __expf(-gt)) * up;
+            } else {
+                v = acc[c][m] * sc0;
+            }
+            if (a.res) v += (float)a.res[(long)m * a.ldr + n];
+            if (a.out_f32) ((float*)a.out)[(long)m * a.ldo + n] = v;
+            else ((bf16*)a.out)[(long)m * a.ldo + n] = (bf16)v;
+        }
+    }
+}
+
+template <bool PAIR> static void wg_llama_gemv_e4m3_launch(const GemvQArgs& a, int M, unsigned blocks, hipStream_t st) {
+    switch (M) {
+        case 1: hipLaunchKernelGGL((wg_llama_gemv_e4m3_kernel<1, PAIR>), dim3(blocks), dim3(256), 0, st, a); break;
+        case 2: hipLaunchKernelGGL((wg_llama_gemv_e4m3_kernel<2, PAIR>), dim3(blocks), dim3(256), 0, st, a); break;
+        case 3: hipLaunchKernelGGL((wg_llama_gemv_e4m3_kernel<3, PAIR>), dim3(blocks), dim3(256), 0, st, a); break;
+        case 4: hipLaunchKernelGGL((wg_llama_gemv_e4m3_kernel<4, PAIR>), dim3(blocks), dim3(256), 0, st, a); break;
+        case 5: hipLaunchKernelGGL((wg_llama_gemv_e4m3_kernel<5, PAIR>), dim3(blocks), dim3(256), 0, st, a); break;
+        case 6: hipLaunchKernelGGL((wg_llama_gemv_e4m3_kernel<6, PAIR>), dim3(blocks), dim3(256), 0, st, a); break;
+        case 7: hipLaunchKernelGGL((wg_llama_gemv_e4m3_kernel<7, PAIR>), dim3(blocks), dim3(256), 0, st, a); break;
+        default: hipLaunchKernelGGL((wg_llama_gemv_e4m3_kernel<8, PAIR>), dim3(blocks), dim3(256), 0, st, a); break;
+    }
+}
+
+template <int M> static void wg_llama_gemv_lora_e4m3_launch_m(const GemvQLoraArgs& a, unsigned blocks, hipStream_t st) {
+    hipLaunchKernelGGL((wg_llama_gemv_e4m3_kernel<M, false, true>), dim3(blocks), dim3(256), 0, st, a);
+}
+
+// the scales of the segments that are there: not null, 4-byte aligned
+static int wg_llama_gemv_scale_check(const char* word, const float* s0, const float* s1, int n1, const float* s2, int n2) {
+    WG_REQUIRE(s0 && (s1 || n1 == 0) && (s2 || n2 == 0), "%s: null scale", word);
+    WG_REQUIRE((((uintptr_t)s0 | (uintptr_t)s1 | (uintptr_t)s2) & 3) == 0, "%s: misaligned scale", word);
+    return 0;
+}
+
+extern "C" int wg_llama_gemv_e4m3(const void* x, long ldx, const void* w0, const float* s0, int n0, const void* w1, const float* s1, int n1,
+                                  const void* w2, const float* s2, int n2, int K, const void* gamma, float eps, const void* residual, long ldr,
+                                  void* out, long ldo, int out_f32, int pair, int M, void* stream) {
+    if (const int rc = wg_llama_gemv_check("llama_gemv_e4m3", x, ldx, w0, n0, w1, n1, w2, n2, K, gamma, residual, ldr, out, ldo, pair, M)) return rc;
+    if (const int rc = wg_llama_gemv_scale_check("llama_gemv_e4m3", s0, s1, n1, s2, n2)) return rc;
+    const long ntot = pair ? n0 : (long)n0 + n1 + n2;
+    GemvQArgs a{{(const bf16*)x, ldx, {(const bf16*)w0, (const bf16*)w1, (const bf16*)w2}, {n0, n1, n2}, K, (const bf16*)gamma, eps,
+                 (const bf16*)residual, ldr, out, ldo, out_f32}, {s0, s1, s2}};
+    const int per_block = 4 * (pair ? 2 : 4);
+    const unsigned blocks = (unsigned)((ntot + per_block - 1) / per_block);
+    if (pair) wg_llama_gemv_e4m3_launch<true>(a, M, blocks, (hipStream_t)stream);
+    else wg_llama_gemv_e4m3_launch<false>(a, M, blocks, (hipStream_t)stream);
+    return wg_check_launch("wg_llama_gemv_e4m3");
+}
+
+extern "C" int wg_llama_gemv_lora_e4m3(const void* x, long ldx, const void* w0, const float* s0, int n0, const void* w1, const float* s1, int n1,
+                                       const void* w2, const float* s2, int n2, int K, const void* gamma, float eps, const void* residual,
+                                       long ldr, void* out, long ldo, int out_f32, int pair, int M, const void* a0, const void* a1,
+                                       const void* a2, int rank, float* t, long ldt, void* stream) {
+    if (const int rc = wg_llama_gemv_check("llama_gemv_lora_e4m3", x, ldx, w0, n0, w1, n1, w2, n2, K, gamma, residual, ldr, out, ldo, pair, M)) return rc;
+    if (const int rc = wg_llama_gemv_scale_check("llama_gemv_lora_e4m3", s0, s1, n1, s2, n2)) return rc;
+    WG_REQUIRE(rank >= 8 && rank <= 64 && rank % 8 == 0, "llama_gemv_lora_e4m3: rank %d must be a multiple of 8, at most 64", rank);
+    WG_REQUIRE(!pair, "llama_gemv_lora_e4m3: pair mode takes no adapters");
+    WG_REQUIRE((!a1 || n1 > 0) && (!a2 || n2 > 0), "llama_gemv_lora_e4m3: an adapter on a segment that is not there");
+    if (a0 || a1 || a2) {
+        WG_REQUIRE(t, "llama_gemv_lora_e4m3: null operand (t, with an adapter given)");
+        WG_REQUIRE(ldt >= 3L * rank && ldt % 4 == 0, "llama_gemv_lora_e4m3: ldt %ld too small for [M, 3 rank] (or not a multiple of 4)", ldt);
+        WG_REQUIRE((((uintptr_t)a0 | (uintptr_t)a1 | (uintptr_t)a2 | (uintptr_t)t) & 15) == 0, "llama_gemv_lora_e4m3: misaligned A / t");
+    }
+    GemvQLoraArgs a{{{(const bf16*)x, ldx, {(const bf16*)w0, (const bf16*)w1, (const bf16*)w2}, {n0, n1, n2}, K, (const bf16*)gamma, eps,
+                      (const bf16*)residual, ldr, out, ldo, out_f32}, {s0, s1, s2}}, {(const bf16*)a0, (const bf16*)a1, (const bf16*)a2}, rank, t, ldt};
+    const long w_waves = ((long)n0 + n1 + n2 + 3) / 4;
+    const long l_waves = ((long)((a0 != nullptr) + (a1 != nullptr) + (a2 != nullptr)) * rank + 3) / 4;
+    const unsigned blocks = (unsigned)((w_waves + l_waves + 3) / 4);
+    const hipStream_t st = (hipStream_t)stream;
+    switch (M) {
+        case 1: wg_llama_gemv_lora_e4m3_launch_m<1>(a, blocks, st); break;
+        case 2: wg_llama_gemv_lora_e4m3_launch_m<2>(a, blocks, st); break;
+        case 3: wg_llama_gemv_lora_e4m3_launch_m<3>(a, blocks, st); break;
+        case 4: wg_llama_gemv_lora_e4m3_launch_m<4>(a, blocks, st); break;
+        case 5: wg_llama_gemv_lora_e4m3_launch_m<5>(a, blocks, st); break;
+        case 6: wg_llama_gemv_lora_e4m3_launch_m<6>(a, blocks, st); break;
+        case 7: wg_llama_gemv_lora_e4m3_launch_m<7>(a, blocks, st); break;
+        default: wg_llama_gemv_lora_e4m3_launch_m<8>(a, blocks, st); break;
+    }
+    return wg_check_launch("wg_llama_gemv_lora_e4m3");
 }
 
 // ---- SiLU(gate) * up on a [M, 2 I] buffer (gate | up), the prefill's MLP middle ------------------------------------------------------

@@ -13,7 +13,17 @@ SwiGLU), gemv (down_proj + residual); then the final RMSNorm into the hidden-sta
 the pick a step needs nothing from the host: the host only looks at the tokens every `sync_every` steps to see whether every row has finished.
 
 Memory kept between calls (one (rows, cap) signature only): the KV cache, 2 * layers * rows * cap * hidden * 2 bytes (a 7B model at cap 896:
-0.47 GB per row), the hidden-state buffer rows * cap * hidden * 2 bytes and a few row-sized work buffers."""
+0.47 GB per row), the hidden-state buffer rows * cap * hidden * 2 bytes and a few row-sized work buffers.
+
+weights="e4m3" (W8A16, decode on half the weight bytes): the seven projections of every layer are kept a second time as OCP e4m3 bytes with
+one power-of-two fp32 scale per output row (the format at include/walkgpt_hip.h; ops.llama_quantize_weight), in a store keyed by each source
+tensor's (data_ptr, _version, dtype): built on first use, and an edited or replaced weight is quantised again -- that one alone -- by the
+same key change that re-captures the graph.  The decode GEMVs read the bytes (wg_llama_gemv_e4m3, with adapters wg_llama_gemv_lora_e4m3); lm_head,
+the embedding, the norms, the LoRA A / B, the KV cache and the attention kernels stay bf16.  The dequantised W' = q * scale is exactly a
+bf16 value, so the mode is an ordinary LLaMA with the weights W': the prefill dequantises each projection into one reused bf16 scratch
+buffer (sized for the largest projection) and runs the bf16 GEMMs on it, the same model the decode step runs.
+Its memory cost: one byte per projection weight plus 4 bytes per output row -- 6.5 GB for a 7B model -- BESIDE the model's own bf16
+tensors, which are not freed and not touched (model_forward and training go on reading them), and the scratch buffer (90 MB at 7B)."""
 import math
 
 import torch
@@ -89,12 +99,57 @@ class _Buffers:
     pass
 
 
+WEIGHT_MODES = ("bf16", "e4m3")
+
+
+def check_weight_mode(weights):
+    if weights not in WEIGHT_MODES:
+        raise ValueError("weights=%r: the HIP LLaMA path takes \"bf16\" or \"e4m3\"" % (weights,))
+    return weights
+
+
+def tensor_key(t):
+    return (t.data_ptr(), t._version, t.dtype)
+
+
+class WeightStore:
+    """What `quantize(tensor)` gave for each source tensor, keyed by tensor_key: refresh(tensors) builds the entries whose key is new (a
+    first use, an in-place edit, a replaced tensor), keeps the others as they are and drops those no tensor has any more."""
+
+    def __init__(self, quantize):
+        self._quantize = quantize
+        self._items = {}
+        self.builds = 0              # how many entries have been built (tests: an edit rebuilds one)
+
+    def refresh(self, tensors):
+        items = {}
+        for t in tensors:
+            k = tensor_key(t)
+            if k in items:
+                continue
+            item = self._items.get(k)
+            if item is None:
+                item = self._quantize(t)
+                self.builds += 1
+            items[k] = item
+        self._items = items
+
+    def __getitem__(self, t):
+        return self._items[tensor_key(t)]
+
+    def __len__(self):
+        return len(self._items)
+
+
 class LlamaHipRunner:
-    def __init__(self, llm):
+    def __init__(self, llm, weights="bf16"):
+        self.weights = check_weight_mode(weights)
         ok, why = self.supports(llm)
         if not ok:
             raise ValueError("LlamaHipRunner: " + why)
         self.llm = llm
+        self._store = WeightStore(ops.llama_quantize_weight) if weights == "e4m3" else None
+        self._scratch = None         # e4m3 prefill: the bf16 buffer every projection is dequantised into
         cfg = llm.config
         self.hidden, self.inter, self.heads = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
         self.eps = float(cfg.rms_norm_eps)
@@ -223,6 +278,30 @@ class LlamaHipRunner:
                 key.append(tuple(None if ad is None else (ad[0], ident(ad[1]), ident(ad[2]), ad[3]) for ad in lw[9]))
         return tuple(key)
 
+    # -- the e4m3 store ----------------------------------------------------------------------------------------------------------------------
+    def _refresh_store(self):
+        """e4m3: (re)quantise the projections whose source tensor is new or has changed; called before anything reads the store."""
+        if self._store is not None:
+            ws = [w for lw in self._layers() for w in lw[1:5] + lw[6:9]]
+            self._store.refresh(ws)
+            self._scratch_numel = max(w.numel() for w in ws)
+
+    def _gemv(self, x, ws, **kw):
+        """The decode GEMV of projection weights `ws`: their bytes and scales in e4m3 mode"""
+        if self._store is None:
+            return ops.llama_gemv(x, ws, **kw)
+        qs = [self._store[w] for w in ws]
+        return ops.llama_gemv(x, [q for q, _ in qs], scales=[s for _, s in qs], **kw)
+
+    def _linear(self, x, w, **kw):
+        """The prefill GEMM of projection weight `w`: in e4m3 mode on W' = q * scale, dequantised into the scratch buffer"""
+        if self._store is None:
+            return ops.linear(x, w, **kw)
+        if self._scratch is None or self._scratch.numel() < self._scratch_numel or self._scratch.device != w.device:
+            self._scratch = torch.empty(self._scratch_numel, device=w.device, dtype=BF16)
+        q, s = self._store[w]
+        return ops.linear(x, ops.llama_dequantize_weight(q, s, out=self._scratch[:w.numel()].view(w.shape)), **kw)
+
     # -- buffers of one (rows, cap) signature ------------------------------------------------------------------------------------------------
     def _buffers(self, rows, cap, dev):
         b = self._buf
@@ -270,6 +349,7 @@ class LlamaHipRunner:
         cap = (L0 + 63) // 64 * 64 if cap is None else cap
         assert cap % 64 == 0 and cap >= L0
         b = self._buffers(rows, cap, inputs_embeds.device)
+        self._refresh_store()
         b.mask.zero_()
         b.mask[:, :L0] = attention_mask.to(torch.uint8)
         M, I, heads = rows * L0, self.inter, self.heads
@@ -283,18 +363,18 @@ class LlamaHipRunner:
         for (ln1, wq, wk, wv, wo, ln2, wg, wu, wd, lora), (kc, vc) in zip(self._layers(), b.kv):
             xn = ops.rmsnorm(h, ln1, self.eps)
             for i, w in enumerate((wq, wk, wv)):
-                ops.linear(xn, w, out=qkv[:, i * H:(i + 1) * H])
+                self._linear(xn, w, out=qkv[:, i * H:(i + 1) * H])
             if lora is None:
                 ops.llama_rope_cache(qkv, b.cos, b.sin, b.zero, q, kc, vc, rows, L0, heads)
             else:
                 ops.llama_rope_cache(qkv, b.cos, b.sin, b.zero, q, kc, vc, rows, L0, heads, t=self._prefill_lora_t(xn, lora, t, tt),
                                      lora_b=[ad and ad[2] for ad in lora], lora_scale=[ad[3] if ad else 0.0 for ad in lora])
             att = ops.llama_attn_prefill(q, kc, vc, b.mask, b.zero, L0, heads, self.scale)
-            h = ops.linear(att, wo, residual=h)
+            h = self._linear(att, wo, residual=h)
             xn = ops.rmsnorm(h, ln2, self.eps)
-            ops.linear(xn, wg, out=gu[:, :I])
-            ops.linear(xn, wu, out=gu[:, I:])
-            h = ops.linear(ops.llama_silu_mul(gu), wd, residual=h)
+            self._linear(xn, wg, out=gu[:, :I])
+            self._linear(xn, wu, out=gu[:, I:])
+            h = self._linear(ops.llama_silu_mul(gu), wd, residual=h)
         norm_w, head_w = self.llm.model.norm.weight, self._head()
         h3 = h.view(rows, L0, H)
         for r in range(rows):
@@ -327,16 +407,16 @@ class LlamaHipRunner:
         past, heads = b.state[0:1], self.heads
         for (ln1, wq, wk, wv, wo, ln2, wg, wu, wd, lora), (kc, vc) in zip(self._layers(), b.kv):
             if lora is None:
-                ops.llama_gemv(b.x, [wq, wk, wv], gamma=ln1, eps=self.eps, out=b.qkv)
+                self._gemv(b.x, [wq, wk, wv], gamma=ln1, eps=self.eps, out=b.qkv)
                 ops.llama_rope_cache(b.qkv, b.cos, b.sin, past, b.q, kc, vc, b.rows, 1, heads)
             else:                                # the adapters ride in the same two launches
-                ops.llama_gemv(b.x, [wq, wk, wv], gamma=ln1, eps=self.eps, out=b.qkv, lora_a=[ad and ad[1] for ad in lora], t_out=b.t)
+                self._gemv(b.x, [wq, wk, wv], gamma=ln1, eps=self.eps, out=b.qkv, lora_a=[ad and ad[1] for ad in lora], t_out=b.t)
                 ops.llama_rope_cache(b.qkv, b.cos, b.sin, past, b.q, kc, vc, b.rows, 1, heads, t=b.t, lora_b=[ad and ad[2] for ad in lora],
                                      lora_scale=[ad[3] if ad else 0.0 for ad in lora])
             ops.llama_attn_decode(b.q, kc, vc, b.mask, past, heads, self.scale, workspace=b.ws, out=b.attn)
-            ops.llama_gemv(b.attn, [wo], residual=b.x, out=b.x)
-            ops.llama_gemv(b.x, [wg, wu], gamma=ln2, eps=self.eps, out=b.act, pair=True)
-            ops.llama_gemv(b.act, [wd], residual=b.x, out=b.x)
+            self._gemv(b.attn, [wo], residual=b.x, out=b.x)
+            self._gemv(b.x, [wg, wu], gamma=ln2, eps=self.eps, out=b.act, pair=True)
+            self._gemv(b.act, [wd], residual=b.x, out=b.x)
         norm_w = self.llm.model.norm.weight
         ops.rmsnorm(b.x, norm_w, self.eps, out=b.hs, slot=past)           # the hidden state of the token at position past_len
         ops.llama_gemv(b.x, [self._head()], gamma=norm_w, eps=self.eps, out=b.logits, out_f32=True)
@@ -380,6 +460,7 @@ class LlamaHipRunner:
         pad = eos if pad is None else pad
         cap = (L0 + max_new_tokens + 63) // 64 * 64
         b = self._buffers(rows, cap, inputs_embeds.device)
+        self._refresh_store()                      # before the capture: a captured step holds the store's buffers
         g = self._captured_step(b, eos, pad) if graph else None
         self.prefill(inputs_embeds, attention_mask, cap=cap)
         b.finished.zero_()

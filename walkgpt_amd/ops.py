@@ -1285,15 +1285,46 @@ def llama_attn_decode(q, k_cache, v_cache, mask, past_len, heads, scale, workspa
     return out
 
 
-def llama_gemv(x, weights, gamma=None, eps=0.0, residual=None, out=None, out_f32=False, pair=False, lora_a=None, t_out=None):
+def llama_quantize_weight(weight):
+    """weight [N, K] bf16 contiguous (K % 16 == 0) -> (q uint8 [N, K], the OCP e4m3 bytes, and scale fp32 [N], a power of two per row):
+    wg_llama_quantize_weight_e4m3, the format at include/walkgpt_hip.h.  Bit-exact."""
+    _need_gpu(weight)
+    assert weight.dtype == _BF16 and weight.dim() == 2 and weight.is_contiguous()
+    N, K = weight.shape
+    q = torch.empty(N, K, device=weight.device, dtype=torch.uint8)
+    scale = torch.empty(N, device=weight.device, dtype=torch.float32)
+    _lib.check(_lib.lib().wg_llama_quantize_weight_e4m3(weight.data_ptr(), q.data_ptr(), scale.data_ptr(), N, K, _stream()),
+               "wg_llama_quantize_weight_e4m3")
+    return q, scale
+
+
+def llama_dequantize_weight(q, scale, out=None):
+    """(q uint8 [N, K], scale fp32 [N]) of llama_quantize_weight -> W' = q * scale as bf16 [N, K], exact (wg_llama_dequantize_weight_bf16)."""
+    _need_gpu(q, scale, out)
+    assert q.dtype == torch.uint8 and q.dim() == 2 and q.is_contiguous()
+    N, K = q.shape
+    assert scale.dtype == torch.float32 and scale.shape == (N,) and scale.is_contiguous()
+    if out is None:
+        out = torch.empty(N, K, device=q.device, dtype=_BF16)
+    assert out.dtype == _BF16 and out.shape == (N, K) and out.is_contiguous()
+    _lib.check(_lib.lib().wg_llama_dequantize_weight_bf16(q.data_ptr(), scale.data_ptr(), out.data_ptr(), N, K, _stream()),
+               "wg_llama_dequantize_weight_bf16")
+    return out
+
+
+def llama_gemv(x, weights, gamma=None, eps=0.0, residual=None, out=None, out_f32=False, pair=False, lora_a=None, t_out=None, scales=None):
     """x [M <= 8, K] against one to three weights [N_i, K] whose outputs sit side by side in `out` [M, sum N_i] (pair: silu(W_0 x) * (W_1 x),
     [M, N_0]).  gamma: RMSNorm prologue; residual: added before the rounding (may be `out`).
     lora_a: per weight an adapter down-projection [r, K] bf16 or None; their products with the same (normalised) input go, fp32, into
-    t_out [M, 3 r], column block i for weight i, in the same launch (wg_llama_gemv_lora_bf16).  lora_a None is the plain entry point."""
+    t_out [M, 3 r], column block i for weight i, in the same launch (wg_llama_gemv_lora_bf16).  lora_a None is the plain entry point.
+    scales: the weights are llama_quantize_weight's e4m3 bytes (uint8) and scales[i] fp32 [N_i] their row scales (wg_llama_gemv_e4m3,
+    wg_llama_gemv_lora_e4m3); None: bf16 weights."""
     weights = list(weights)
     _need_gpu(x, gamma, residual, out, *weights)
     assert x.dtype == _BF16 and 1 <= len(weights) <= 3
     M, K, ldx = _rows(x)
+    if scales is not None:
+        return _llama_gemv_e4m3(x, weights, list(scales), gamma, eps, residual, out, out_f32, pair, lora_a, t_out)
     for w in weights:
         assert w.dtype == _BF16 and w.dim() == 2 and w.shape[1] == K and w.is_contiguous()
     ns = [int(w.shape[0]) for w in weights] + [0] * (3 - len(weights))
@@ -1321,6 +1352,44 @@ def llama_gemv(x, weights, gamma=None, eps=0.0, residual=None, out=None, out_f32
                                                   _ptr(residual), _residual_ld(residual), out.data_ptr(), ldo, 1 if out_f32 else 0,
                                                   1 if pair else 0, M, _ptr(lora_a[0]), _ptr(lora_a[1]), _ptr(lora_a[2]), rank, _ptr(t_out),
                                                   0 if t_out is None else t_out.stride(0), _stream()), "wg_llama_gemv_lora_bf16")
+    return out
+
+
+def _llama_gemv_e4m3(x, weights, scales, gamma, eps, residual, out, out_f32, pair, lora_a, t_out):
+    """llama_gemv's byte-weight form (its checks on x, gamma and residual are done)."""
+    _need_gpu(*scales)
+    M, K, ldx = _rows(x)
+    assert len(scales) == len(weights)
+    for w, s in zip(weights, scales):
+        assert w.dtype == torch.uint8 and w.dim() == 2 and w.shape[1] == K and w.is_contiguous()
+        assert s.dtype == torch.float32 and s.shape == (w.shape[0],) and s.is_contiguous()
+    ns = [int(w.shape[0]) for w in weights] + [0] * (3 - len(weights))
+    N = ns[0] if pair else sum(ns)
+    if out is None:
+        out = torch.empty(M, N, device=x.device, dtype=torch.float32 if out_f32 else _BF16)
+    Mo, No, ldo = _rows(out)
+    assert (Mo, No) == (M, N) and out.dtype == (torch.float32 if out_f32 else _BF16)
+    assert gamma is None or (gamma.dtype == _BF16 and gamma.numel() == K and gamma.is_contiguous())
+    assert residual is None or residual.shape[-1] == N
+    ptrs = [w.data_ptr() for w in weights] + [0] * (3 - len(weights))
+    sp = [s.data_ptr() for s in scales] + [0] * (3 - len(scales))
+    if lora_a is None:
+        assert t_out is None
+        _lib.check(_lib.lib().wg_llama_gemv_e4m3(x.data_ptr(), ldx, ptrs[0], sp[0], ns[0], ptrs[1], sp[1], ns[1], ptrs[2], sp[2], ns[2], K,
+                                                 _ptr(gamma), float(eps), _ptr(residual), _residual_ld(residual), out.data_ptr(), ldo,
+                                                 1 if out_f32 else 0, 1 if pair else 0, M, _stream()), "wg_llama_gemv_e4m3")
+        return out
+    lora_a = list(lora_a) + [None] * (3 - len(lora_a))
+    assert len(lora_a) == 3
+    _need_gpu(t_out, *lora_a)
+    rank = _lora_rank(lora_a, 0, K, t_out)
+    assert t_out is None or (t_out.dtype == torch.float32 and t_out.dim() == 2 and t_out.stride(1) == 1 and t_out.shape == (M, 3 * rank))
+    assert t_out is not None or all(a is None for a in lora_a)
+    _lib.check(_lib.lib().wg_llama_gemv_lora_e4m3(x.data_ptr(), ldx, ptrs[0], sp[0], ns[0], ptrs[1], sp[1], ns[1], ptrs[2], sp[2], ns[2], K,
+                                                  _ptr(gamma), float(eps), _ptr(residual), _residual_ld(residual), out.data_ptr(), ldo,
+                                                  1 if out_f32 else 0, 1 if pair else 0, M, _ptr(lora_a[0]), _ptr(lora_a[1]), _ptr(lora_a[2]),
+                                                  rank, _ptr(t_out), 0 if t_out is None else t_out.stride(0), _stream()),
+               "wg_llama_gemv_lora_e4m3")
     return out
 
 
