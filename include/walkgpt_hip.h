@@ -59,6 +59,13 @@ int wg_gemm_pick_tile(int M, int N);
 int wg_gemm_pick_tile_ex(int M, int N, int allow_tail);
 /* the same with K in view: the kernel id wg_gemm_bias_act_bf16 really launches (the skinny kernel 5 needs K % 128 == 0, else tile 1) */
 int wg_gemm_pick_tile_mnk(int M, int N, int K, int allow_tail);
+/* the route a call of wg_gemm_bias_act_bf16 really takes, by the launcher's own decision: the pick above (tile_hint <= 0) or the caller's hint,
+ * after the fallbacks for operands a kernel cannot take (16 -> 14, 11 / 12 -> 1, 5 -> 1, anything off the MFMA rules -> 3).  Returns the
+ * kernel id, + 64 when that kernel runs the staged (LDS-transposed, 16-byte) epilogue, which adds a residual to the already bf16-rounded
+ * tile.  align_bits: the low four address bits of A, W, C, bias and the residual in bits 0-3, 4-7, 8-11, 12-15, 16-19 (absent operand: 0).
+ * Launches nothing.  Only adds a symbol: wg_version() stays 300. */
+int wg_gemm_route_of(int M, int N, int K, long lda, long ldw, long ldc, long ldr, int has_residual, int res_row_mod, int out_f32,
+                     unsigned align_bits, int tile_hint);
 int wg_gemm_bias_act_bf16(const void* A, long lda, const void* W, long ldw, const void* bias, const void* residual,
                           long ldr, int res_row_mod, void* C, long ldc, int M, int N, int K, int act, int out_f32,
                           int tile_hint, void* stream);

@@ -163,62 +163,66 @@ def test_clip_tower_resizes_a_stock_position_table_on_load():
 # wg_gemm_pick_tile_mnk (allow_tail 0 / 1), wg_gemm_ln_supported, wg_gemm_row_partials_supported, wg_gemm_skinny_ln_supported and
 # ops.gemm_tile_for (tail_tiles False / True) return.  Kernel ids: 1 = 128x128 tiles, 3 = row-wave, 5 = skinny, 11 = persistent 128x128,
 # 12 = 128x128 with the M % 128 <= 16 leftover rows in the last row tile, 16 = persistent 256x256.
+# Eleventh column: the route the launcher really takes (wg_gemm_route_of, fed ops.gemm_tile_for's answer as ops.linear feeds it) for a bf16
+# output and 16-byte aligned operands, a residual where ldr != 0: the kernel id after the fallbacks (14 = one-tile 256x256 ping-pong, where 16
+# cannot take the operands), + _S where that kernel runs the staged epilogue.
 _E = 1 << 20
+_S = 64
 _GEMM_QUERIES = [
     # M <= 16: the skinny kernel when N % 16 == 0, and only at K % 128 == 0 (K = 192 takes the 128x128 tiles)
-    ((8, 256, 256, 256, 256, 256, 0), (5, 5, 5, 5, 5, 0, 0, 1, 5, 5)),
-    ((8, 256, 192, 192, 192, 256, 0), (5, 5, 5, 1, 1, 0, 0, 0, 1, 1)),
-    ((16, 4096, 4096, 4096, 4096, 4096, 0), (5, 5, 5, 5, 5, 0, 0, 1, 5, 5)),
-    ((8, 100, 256, 256, 256, 100, 0), (1, 1, 1, 1, 1, 0, 0, 0, 1, 1)),
-    ((1, 16, 128, 128, 128, 16, 0), (5, 5, 5, 5, 5, 0, 0, 1, 5, 5)),
-    ((0, 256, 256, 256, 256, 256, 0), (5, 5, 5, 5, 5, 0, 0, 0, 5, 5)),
-    ((8, 256, 256, 260, 256, 256, 0), (5, 5, 5, 5, 5, 0, 0, 0, 3, 3)),
-    ((8, 256, 256, 256, 256, 258, 0), (5, 5, 5, 5, 5, 0, 0, 0, 3, 3)),
+    ((8, 256, 256, 256, 256, 256, 0), (5, 5, 5, 5, 5, 0, 0, 1, 5, 5, 5)),
+    ((8, 256, 192, 192, 192, 256, 0), (5, 5, 5, 1, 1, 0, 0, 0, 1, 1, 1 + _S)),
+    ((16, 4096, 4096, 4096, 4096, 4096, 0), (5, 5, 5, 5, 5, 0, 0, 1, 5, 5, 5)),
+    ((8, 100, 256, 256, 256, 100, 0), (1, 1, 1, 1, 1, 0, 0, 0, 1, 1, 1)),
+    ((1, 16, 128, 128, 128, 16, 0), (5, 5, 5, 5, 5, 0, 0, 1, 5, 5, 5)),
+    ((0, 256, 256, 256, 256, 256, 0), (5, 5, 5, 5, 5, 0, 0, 0, 5, 5, 5)),
+    ((8, 256, 256, 260, 256, 256, 0), (5, 5, 5, 5, 5, 0, 0, 0, 3, 3, 3)),
+    ((8, 256, 256, 256, 256, 258, 0), (5, 5, 5, 5, 5, 0, 0, 0, 3, 3, 3)),
     # 17 <= M <= 128: 128x128 tiles, or the skinny kernel where its cost model says it wins
-    ((17, 1024, 1024, 1024, 1024, 1024, 0), (1, 1, 1, 5, 5, 0, 0, 1, 5, 5)),
-    ((32, 4096, 4096, 4096, 4096, 4096, 0), (1, 1, 1, 5, 5, 0, 0, 1, 5, 5)),
-    ((96, 1024, 1024, 1024, 1024, 1024, 0), (1, 1, 1, 5, 5, 0, 0, 1, 5, 5)),
-    ((128, 256, 5120, 5120, 5120, 256, 0), (1, 1, 1, 5, 5, 0, 0, 1, 5, 5)),
-    ((64, 256, 192, 192, 192, 256, 0), (1, 1, 1, 1, 1, 0, 0, 0, 1, 1)),
-    ((100, 4096, 4096, 4104, 4096, 4096, 4096), (1, 1, 1, 1, 1, 0, 0, 1, 1, 1)),
-    ((128, 8192, 256, 256, 256, 8192, 0), (1, 1, 1, 5, 5, 0, 0, 1, 5, 5)),
-    ((128, 16384, 256, 256, 256, 16384, 0), (1, 1, 1, 1, 1, 0, 0, 1, 1, 1)),
-    ((129, 256, 256, 256, 256, 256, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11)),
+    ((17, 1024, 1024, 1024, 1024, 1024, 0), (1, 1, 1, 5, 5, 0, 0, 1, 5, 5, 5)),
+    ((32, 4096, 4096, 4096, 4096, 4096, 0), (1, 1, 1, 5, 5, 0, 0, 1, 5, 5, 5)),
+    ((96, 1024, 1024, 1024, 1024, 1024, 0), (1, 1, 1, 5, 5, 0, 0, 1, 5, 5, 5)),
+    ((128, 256, 5120, 5120, 5120, 256, 0), (1, 1, 1, 5, 5, 0, 0, 1, 5, 5, 5)),
+    ((64, 256, 192, 192, 192, 256, 0), (1, 1, 1, 1, 1, 0, 0, 0, 1, 1, 1 + _S)),
+    ((100, 4096, 4096, 4104, 4096, 4096, 4096), (1, 1, 1, 1, 1, 0, 0, 1, 1, 1, 1 + _S)),
+    ((128, 8192, 256, 256, 256, 8192, 0), (1, 1, 1, 5, 5, 0, 0, 1, 5, 5, 5)),
+    ((128, 16384, 256, 256, 256, 16384, 0), (1, 1, 1, 1, 1, 0, 0, 1, 1, 1, 1 + _S)),
+    ((129, 256, 256, 256, 256, 256, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11, 11 + _S)),
     # M = 8 * 1025 and other M % 128 in 1..16: the tail kernel (12) only with allow_tail, N % 8 == 0, and when it fills the chip
-    ((8200, 1024, 1024, 1024, 1024, 1024, 0), (16, 16, 12, 16, 12, 1, 1, 0, 16, 12)),
-    ((8200, 3072, 1024, 1024, 1024, 3072, 0), (16, 16, 12, 16, 12, 1, 0, 0, 16, 12)),
-    ((8200, 4096, 1024, 1024, 1024, 4096, 4096), (16, 16, 12, 16, 12, 1, 0, 0, 16, 12)),
-    ((8200, 1028, 1024, 1024, 1024, 1028, 0), (16, 16, 16, 16, 16, 0, 0, 0, 16, 16)),
-    ((2050, 1024, 1024, 1024, 1024, 1024, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11)),
-    ((4112, 768, 768, 768, 768, 768, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11)),
-    ((4113, 768, 768, 768, 768, 768, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11)),
+    ((8200, 1024, 1024, 1024, 1024, 1024, 0), (16, 16, 12, 16, 12, 1, 1, 0, 16, 12, 16 + _S)),
+    ((8200, 3072, 1024, 1024, 1024, 3072, 0), (16, 16, 12, 16, 12, 1, 0, 0, 16, 12, 16 + _S)),
+    ((8200, 4096, 1024, 1024, 1024, 4096, 4096), (16, 16, 12, 16, 12, 1, 0, 0, 16, 12, 16 + _S)),
+    ((8200, 1028, 1024, 1024, 1024, 1028, 0), (16, 16, 16, 16, 16, 0, 0, 0, 16, 16, 14)),
+    ((2050, 1024, 1024, 1024, 1024, 1024, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11, 11 + _S)),
+    ((4112, 768, 768, 768, 768, 768, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11, 11 + _S)),
+    ((4113, 768, 768, 768, 768, 768, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11, 11 + _S)),
     # N = 128 / 384 / < 256: 128x128 persistent tiles; N >= 256: 256x256 unless too few big tiles (or, with allow_tail, worse rounds)
-    ((4096, 128, 256, 256, 256, 128, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11)),
-    ((4096, 384, 768, 768, 768, 384, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11)),
-    ((4096, 192, 256, 256, 256, 192, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11)),
-    ((4096, 64, 64, 64, 64, 64, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11)),
-    ((1024, 1024, 1024, 1024, 1024, 1024, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11)),
-    ((32768, 768, 768, 768, 768, 768, 768), (16, 16, 11, 16, 11, 1, 1, 0, 16, 11)),
-    ((32768, 2304, 768, 768, 768, 2304, 0), (16, 16, 16, 16, 16, 1, 0, 0, 16, 16)),
-    ((32768, 1280, 5120, 5120, 5120, 1280, 1280), (16, 16, 16, 16, 16, 1, 1, 0, 16, 16)),
-    ((32768, 1536, 768, 768, 768, 1536, 0), (16, 16, 16, 16, 16, 1, 0, 0, 16, 16)),
-    ((32768, 1152, 768, 768, 768, 1152, 0), (16, 16, 16, 16, 16, 1, 0, 0, 16, 16)),
-    ((16384, 1536, 768, 768, 768, 1536, 0), (16, 16, 11, 16, 11, 1, 0, 0, 16, 11)),
+    ((4096, 128, 256, 256, 256, 128, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11, 11 + _S)),
+    ((4096, 384, 768, 768, 768, 384, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11, 11 + _S)),
+    ((4096, 192, 256, 256, 256, 192, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11, 11 + _S)),
+    ((4096, 64, 64, 64, 64, 64, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11, 11 + _S)),
+    ((1024, 1024, 1024, 1024, 1024, 1024, 0), (11, 11, 11, 11, 11, 0, 0, 0, 11, 11, 11 + _S)),
+    ((32768, 768, 768, 768, 768, 768, 768), (16, 16, 11, 16, 11, 1, 1, 0, 16, 11, 16 + _S)),
+    ((32768, 2304, 768, 768, 768, 2304, 0), (16, 16, 16, 16, 16, 1, 0, 0, 16, 16, 16 + _S)),
+    ((32768, 1280, 5120, 5120, 5120, 1280, 1280), (16, 16, 16, 16, 16, 1, 1, 0, 16, 16, 16 + _S)),
+    ((32768, 1536, 768, 768, 768, 1536, 0), (16, 16, 16, 16, 16, 1, 0, 0, 16, 16, 16 + _S)),
+    ((32768, 1152, 768, 768, 768, 1152, 0), (16, 16, 16, 16, 16, 1, 0, 0, 16, 16, 16 + _S)),
+    ((16384, 1536, 768, 768, 768, 1536, 0), (16, 16, 11, 16, 11, 1, 0, 0, 16, 11, 16 + _S)),
     # padded and odd leading dimensions, K off the MFMA path's K % 64 rule
-    ((4096, 1024, 1024, 1028, 1024, 1024, 0), (16, 16, 11, 16, 11, 0, 0, 0, 3, 3)),
-    ((4096, 1024, 1024, 1024, 1030, 1024, 0), (16, 16, 11, 16, 11, 0, 0, 0, 3, 3)),
-    ((4096, 1024, 1024, 1024, 1024, 1028, 0), (16, 16, 11, 16, 11, 0, 0, 0, 16, 11)),
-    ((4096, 1024, 1024, 1024, 1024, 1030, 0), (16, 16, 11, 16, 11, 0, 0, 0, 3, 3)),
-    ((4096, 1024, 1024, 1024, 1024, 1024, 1026), (16, 16, 11, 16, 11, 1, 1, 0, 3, 3)),
-    ((4096, 1024, 1000, 1000, 1000, 1024, 0), (16, 16, 11, 16, 11, 0, 0, 0, 3, 3)),
-    ((4096, 1024, 1024, 1536, 1152, 1280, 1032), (16, 16, 11, 16, 11, 1, 1, 0, 16, 11)),
+    ((4096, 1024, 1024, 1028, 1024, 1024, 0), (16, 16, 11, 16, 11, 0, 0, 0, 3, 3, 3)),
+    ((4096, 1024, 1024, 1024, 1030, 1024, 0), (16, 16, 11, 16, 11, 0, 0, 0, 3, 3, 3)),
+    ((4096, 1024, 1024, 1024, 1024, 1028, 0), (16, 16, 11, 16, 11, 0, 0, 0, 16, 11, 14)),
+    ((4096, 1024, 1024, 1024, 1024, 1030, 0), (16, 16, 11, 16, 11, 0, 0, 0, 3, 3, 3)),
+    ((4096, 1024, 1024, 1024, 1024, 1024, 1026), (16, 16, 11, 16, 11, 1, 1, 0, 3, 3, 3)),
+    ((4096, 1024, 1000, 1000, 1000, 1024, 0), (16, 16, 11, 16, 11, 0, 0, 0, 3, 3, 3)),
+    ((4096, 1024, 1024, 1536, 1152, 1280, 1032), (16, 16, 11, 16, 11, 1, 1, 0, 16, 11, 16 + _S)),
     # the persistent kernel's 4 GiB operand bound ((M + 256) * lda, (N + 256) * ldw below 2^31 elements) and C's 2 GiB extent
-    ((_E - 257, 1024, 2048, 2048, 2048, 1024, 0), (16, 16, 16, 16, 16, 1, 1, 0, 16, 16)),
-    ((_E - 256, 1024, 2048, 2048, 2048, 1024, 0), (16, 16, 16, 16, 16, 0, 0, 0, 16, 16)),
-    ((1000, _E - 264, 2048, 2048, 2048, _E - 264, 0), (16, 16, 16, 16, 16, 1, 0, 0, 16, 16)),
-    ((1000, _E - 256, 2048, 2048, 2048, _E - 256, 0), (16, 16, 16, 16, 16, 0, 0, 0, 16, 16)),
-    ((32768, 1024, 1024, 1024, 1024, 32768, 0), (16, 16, 16, 16, 16, 1, 1, 0, 16, 16)),
-    ((32768, 1024, 1024, 1024, 1024, 40960, 0), (16, 16, 16, 16, 16, 0, 0, 0, 16, 16)),
+    ((_E - 257, 1024, 2048, 2048, 2048, 1024, 0), (16, 16, 16, 16, 16, 1, 1, 0, 16, 16, 16 + _S)),
+    ((_E - 256, 1024, 2048, 2048, 2048, 1024, 0), (16, 16, 16, 16, 16, 0, 0, 0, 16, 16, 14 + _S)),
+    ((1000, _E - 264, 2048, 2048, 2048, _E - 264, 0), (16, 16, 16, 16, 16, 1, 0, 0, 16, 16, 16 + _S)),
+    ((1000, _E - 256, 2048, 2048, 2048, _E - 256, 0), (16, 16, 16, 16, 16, 0, 0, 0, 16, 16, 14 + _S)),
+    ((32768, 1024, 1024, 1024, 1024, 32768, 0), (16, 16, 16, 16, 16, 1, 1, 0, 16, 16, 16 + _S)),
+    ((32768, 1024, 1024, 1024, 1024, 40960, 0), (16, 16, 16, 16, 16, 0, 0, 0, 16, 16, 14)),
 ]
 
 
@@ -231,7 +235,8 @@ def _gemm_query_mismatches(columns):
                L.wg_gemm_pick_tile_mnk(M, N, K, 0), L.wg_gemm_pick_tile_mnk(M, N, K, 1),
                L.wg_gemm_ln_supported(M, N, K, lda, ldw, ldc), L.wg_gemm_row_partials_supported(M, N, K, lda, ldw, ldc),
                L.wg_gemm_skinny_ln_supported(M, N, K, lda, ldw, ldc),
-               ops.gemm_tile_for(M, N, K, lda, ldw, ldc, ldr), ops.gemm_tile_for(M, N, K, lda, ldw, ldc, ldr, True))
+               ops.gemm_tile_for(M, N, K, lda, ldw, ldc, ldr), ops.gemm_tile_for(M, N, K, lda, ldw, ldc, ldr, True),
+               L.wg_gemm_route_of(M, N, K, lda, ldw, ldc, ldr, 1 if ldr else 0, 0, 0, 0, ops.gemm_tile_for(M, N, K, lda, ldw, ldc, ldr)))
         if [got[i] for i in columns] != [want[i] for i in columns]:
             bad.append(((M, N, K, lda, ldw, ldc, ldr), [want[i] for i in columns], [got[i] for i in columns]))
     return bad
@@ -242,6 +247,67 @@ def test_tile_selector_sees_k():
     K % 128 == 0; K = 192 passes the MFMA path's K % 64 rule and runs on the 128x128 tiles (1).  Pinned over _GEMM_QUERIES for
     wg_gemm_pick_tile, _ex, _mnk and ops.gemm_tile_for."""
     assert _gemm_query_mismatches([0, 1, 2, 3, 4, 8, 9]) == []
+
+
+# wg_gemm_route_of beyond the bf16 / aligned column: (M, N, K, lda, ldw, ldc, ldr, has_residual, res_row_mod, out_f32, align_bits, tile_hint) -> route.
+# align_bits: low address bits of A | W << 4 | C << 8 | bias << 12 | R << 16.
+_GEMM_ROUTES = [
+    # an fp32 output fails the staged epilogue: 16 -> 14, 11 / 12 -> 1, all unstaged; 1, 2, 14 keep their kernel
+    ((8200, 1024, 1024, 1024, 1024, 1024, 0, 0, 0, 1, 0, 16), 14),
+    ((8200, 1024, 1024, 1024, 1024, 1024, 0, 0, 0, 1, 0, 0), 14),
+    ((300, 272, 128, 128, 128, 272, 0, 0, 0, 1, 0, 16), 14),
+    ((300, 272, 128, 128, 128, 272, 0, 0, 0, 1, 0, 11), 1),
+    ((4096, 128, 256, 256, 256, 128, 0, 0, 0, 1, 0, 0), 1),
+    ((8200, 1024, 1024, 1024, 1024, 1024, 0, 0, 0, 1, 0, 12), 1),
+    ((300, 272, 128, 128, 128, 272, 0, 0, 0, 1, 0, 1), 1),
+    ((300, 272, 128, 128, 128, 272, 0, 0, 0, 1, 0, 2), 2),
+    ((300, 272, 128, 128, 128, 272, 0, 0, 0, 1, 0, 14), 14),
+    # the same calls with a bf16 output: the kernel asked for, staged
+    ((300, 272, 128, 128, 128, 272, 0, 0, 0, 0, 0, 16), 16 + _S),
+    ((300, 272, 128, 128, 128, 272, 0, 0, 0, 0, 0, 11), 11 + _S),
+    ((300, 272, 128, 128, 128, 272, 0, 0, 0, 0, 0, 1), 1 + _S),
+    ((300, 272, 128, 128, 128, 272, 0, 0, 0, 0, 0, 2), 2 + _S),
+    ((300, 272, 128, 128, 128, 272, 0, 0, 0, 0, 0, 14), 14 + _S),
+    ((8200, 1024, 1024, 1024, 1024, 1024, 0, 0, 0, 0, 0, 12), 12 + _S),
+    ((300, 272, 128, 128, 128, 272, 0, 0, 0, 0, 0, 12), 1 + _S),                  # 300 % 128 = 44 leftover rows: not the tail kernel's
+    # alignment: an 8-byte aligned bias keeps 16 out (14, still staged); an 8-byte aligned residual or ldr % 8 != 0 unstages; 4-byte alignment of A,
+    # W or C, or 2-byte alignment of bias or R, leaves the MFMA path
+    ((300, 272, 128, 128, 128, 272, 0, 0, 0, 0, 8 << 12, 16), 14 + _S),
+    ((300, 272, 128, 128, 128, 272, 272, 1, 0, 0, 8 << 16, 16), 14),
+    ((300, 272, 128, 128, 128, 272, 272, 1, 0, 0, 8 << 16, 11), 1),
+    ((300, 272, 128, 128, 128, 272, 276, 1, 0, 0, 0, 16), 14),
+    ((300, 272, 128, 128, 128, 272, 272, 1, 0, 0, 0, 16), 16 + _S),
+    ((300, 272, 128, 128, 128, 272, 272, 0, 0, 0, 8 << 16, 16), 16 + _S),         # no residual: its bits are not looked at
+    ((300, 272, 128, 128, 128, 272, 0, 0, 0, 0, 8, 16), 3),
+    ((300, 272, 128, 128, 128, 272, 0, 0, 0, 0, 8 << 4, 16), 3),
+    ((300, 272, 128, 128, 128, 272, 0, 0, 0, 0, 8 << 8, 16), 3),
+    ((300, 272, 128, 128, 128, 272, 0, 0, 0, 0, 4 << 12, 16), 3),
+    ((300, 272, 128, 128, 128, 272, 272, 1, 0, 0, 4 << 16, 16), 3),
+    # N % 8 != 0 unstages; a residual table (res_row_mod) is measured by the rows that are read: 2^20 output rows of a 1024-column residual are
+    # 2 GiB, too far for the staged epilogue's 32-bit offsets, 4096 table rows are not
+    ((300, 276, 128, 128, 128, 276, 0, 0, 0, 0, 0, 16), 14),
+    ((_E - 512, 1024, 64, 64, 64, 1024, 1024, 1, 0, 0, 0, 16), 16 + _S),
+    ((_E, 1024, 64, 64, 64, 1024, 1024, 1, 4096, 0, 0, 16), 14),                  # (C itself is 2 GiB here)
+    ((_E - 512, 1024, 64, 64, 64, 1024, 2048, 1, 0, 0, 0, 16), 14),
+    ((_E - 512, 1024, 64, 64, 64, 1024, 2048, 1, 4096, 0, 0, 16), 16 + _S),
+    # hints: 3 is honoured, 5 only for skinny shapes, an unknown one means the 128x128 tiles
+    ((300, 272, 128, 128, 128, 272, 0, 0, 0, 0, 0, 3), 3),
+    ((300, 272, 128, 128, 128, 272, 0, 0, 0, 0, 0, 5), 1 + _S),
+    ((16, 272, 128, 128, 128, 272, 0, 0, 0, 0, 0, 5), 5),
+    ((300, 272, 128, 128, 128, 272, 0, 0, 0, 0, 0, 7), 1 + _S),
+]
+
+
+def test_gemm_route_query_is_the_launchers_decision():
+    """wg_gemm_route_of answers with the kernel wg_gemm_bias_act_bf16 launches (the launcher calls the same wg_gemm_decide) and whether it runs
+    the staged epilogue.  The eleventh column of _GEMM_QUERIES pins it for bf16 outputs -- the row with ldc = 1028 runs 14 where
+    ops.gemm_tile_for says 16 --, _GEMM_ROUTES the fallbacks an fp32 output, alignment, N % 8 and the 2 GiB extents cause."""
+    from walkgpt_amd import _lib
+    assert _gemm_query_mismatches([10]) == []
+    L = _lib.lib()
+    bad = [(args, want, L.wg_gemm_route_of(*args)) for args, want in _GEMM_ROUTES if L.wg_gemm_route_of(*args) != want]
+    assert bad == []
+    assert L.wg_version() == 300            # the query only adds a symbol
 
 
 @pytest.mark.parametrize("name", ["w56", "w448"])

@@ -27,8 +27,15 @@ def test_gemm_exact_integer_asymmetric(dev, tile):
     w = torch.randint(-3, 4, (N, K), generator=g).float()
     w[:, 0] += torch.arange(N).float() % 5
     ref = a @ w.t()
-    out = ops.linear(a.to(dev, torch.bfloat16), w.to(dev, torch.bfloat16), out_f32=True, tile=tile)
+    ad, wd = a.to(dev, torch.bfloat16), w.to(dev, torch.bfloat16)
+    # an fp32 output cannot take the staged epilogue: 11 runs as 1 and 16 as 14 (wg_gemm_route), all through the unstaged epilogue
+    assert ops.gemm_route(ad, wd, tile=tile, out_f32=True) == {1: 1, 2: 2, 14: 14, 11: 1, 16: 14}[tile]
+    out = ops.linear(ad, wd, out_f32=True, tile=tile)
     assert torch.equal(out.cpu(), ref)
+    # the bf16-output twin runs the kernel the parameter names, staged epilogue: the same sums, rounded once to bf16
+    assert ops.gemm_route(ad, wd, tile=tile) == tile | ops.GEMM_STAGED
+    out16 = ops.linear(ad, wd, tile=tile)
+    assert torch.equal(out16.cpu(), ref.to(torch.bfloat16))
 
 
 @pytest.mark.parametrize("M,N,K,tile", [(8200, 1024, 1024, 1), (8200, 3072, 1024, 2), (4096, 768, 3072, 2),

@@ -1788,8 +1788,8 @@ static int launch_pp_persist(GemmArgs& g, hipStream_t st) {
 }
 
 template <int BM, int BN, int BK, int STAGES, int WM, int WN, int PIPE = 0>
-static int launch_tile(GemmArgs& g, hipStream_t st) {
-    return wg_staged_ok(g) ? launch_tile_impl<BM, BN, BK, STAGES, WM, WN, true, PIPE>(g, st)
+static int launch_tile(GemmArgs& g, hipStream_t st, bool staged) {
+    return staged ? launch_tile_impl<BM, BN, BK, STAGES, WM, WN, true, PIPE>(g, st)
                            : launch_tile_impl<BM, BN, BK, STAGES, WM, WN, false, PIPE>(g, st);
 }
 
@@ -1898,6 +1898,15 @@ static GemmArgs wg_gemm_args(const void* A, long lda, const void* W, long ldw, v
     return g;
 }
 
+// The launcher's decision, in one place for wg_gemm_launch and the wg_gemm_route_of query: fills the extents, picks the kernel and says whether
+// it runs the staged epilogue (11, 12 and 16 have no other; 1, 2 and 14 take it when wg_staged_ok; 3 and 5 never).
+static int wg_gemm_decide(GemmArgs& g, int tile_hint, bool* staged) {
+    wg_gemm_extents(g);
+    const int tile = wg_gemm_route(g, tile_hint);
+    *staged = tile == 11 || tile == 12 || tile == 16 || ((tile == 1 || tile == 2 || tile == 14) && wg_staged_ok(g));
+    return tile;
+}
+
 // The bf16 entry points' common checks, then the kernel wg_gemm_route picks.
 static int wg_gemm_launch(GemmArgs& g, int tile_hint, hipStream_t st) {
     WG_REQUIRE(g.A && g.W && g.C, "gemm: null operand");
@@ -1905,8 +1914,8 @@ static int wg_gemm_launch(GemmArgs& g, int tile_hint, hipStream_t st) {
     WG_REQUIRE(g.act >= 0 && g.act <= 3, "gemm: bad activation %d", g.act);
     WG_REQUIRE(g.lda >= g.K && g.ldw >= g.K && g.ldc >= g.N, "gemm: leading dimension smaller than the row");
     WG_REQUIRE(!g.R || g.ldr >= g.N, "gemm: residual leading dimension smaller than N");
-    wg_gemm_extents(g);
-    const int tile = wg_gemm_route(g, tile_hint);
+    bool staged = false;
+    const int tile = wg_gemm_decide(g, tile_hint, &staged);
     // (the row statistics' producer and consumers are epilogues of kernel 16; 14 is where a call asking for 16 lands otherwise)
     WG_REQUIRE(tile != 14 || !(g.ln_part || g.stats_part || g.ln_stats), "gemm: this operand layout cannot take the persistent kernel's staged epilogue");
     switch (tile) {
@@ -1932,10 +1941,10 @@ static int wg_gemm_launch(GemmArgs& g, int tile_hint, hipStream_t st) {
             return wg_check_launch("wg_gemm_bias_act_bf16(skinny)");
         case 12: return launch_tail(g, st);                            // 128x128 tiles, last row tile absorbs M % 128 <= 16 rows
         case 11: return launch_persist<128, 128, 2, 2>(g, st);         // persistent 128x128 tiles, 2 workgroups / CU
-        case 2: return launch_tile<256, 256, 64, 2, 2, 4>(g, st);      // 256x256, plain two-slab loop (best at K >= 8192)
-        case 14: return launch_tile<256, 256, 64, 2, 2, 4, 2>(g, st);  // 256x256, ping-pong between the two waves of each SIMD
+        case 2: return launch_tile<256, 256, 64, 2, 2, 4>(g, st, staged);      // 256x256, plain two-slab loop (best at K >= 8192)
+        case 14: return launch_tile<256, 256, 64, 2, 2, 4, 2>(g, st, staged);  // 256x256, ping-pong between the two waves of each SIMD
         case 16: return launch_pp_persist(g, st);                      // the same loop, persistent tiles (first slab / store drain hidden)
-        default: return launch_tile<128, 128, 64, 2, 2, 2>(g, st);  //  64 KiB LDS, 4 waves, 2 workgroups / CU
+        default: return launch_tile<128, 128, 64, 2, 2, 2>(g, st, staged);  //  64 KiB LDS, 4 waves, 2 workgroups / CU
     }
 }
 
@@ -1945,6 +1954,21 @@ extern "C" int wg_gemm_bias_act_bf16(const void* A, long lda, const void* W, lon
     GemmArgs g = wg_gemm_args(A, lda, W, ldw, C, ldc, M, N, K, act);
     g.bias = (const bf16*)bias; g.R = (const bf16*)residual; g.ldr = ldr; g.res_mod = res_row_mod; g.out_f32 = out_f32;
     return wg_gemm_launch(g, tile_hint, (hipStream_t)stream);
+}
+
+// The kernel wg_gemm_bias_act_bf16 launches for a call of this shape, these leading dimensions and this operand alignment, + 64 when that
+// kernel runs the staged epilogue (wg_gemm_decide, the launcher's own decision).  align_bits: the low four address bits of A, W, C, bias and
+// the residual in bits 0-3, 4-7, 8-11, 12-15 and 16-19 (absent operands: 0).  Nothing is launched and no pointer is read.
+extern "C" int wg_gemm_route_of(int M, int N, int K, long lda, long ldw, long ldc, long ldr, int has_residual, int res_row_mod, int out_f32,
+                                unsigned align_bits, int tile_hint) {
+    alignas(16) static char at[32];   // stands for the operands: only their alignment (and whether R is there) is looked at
+    GemmArgs g = wg_gemm_args(at + (align_bits & 15), lda, at + ((align_bits >> 4) & 15), ldw, at + ((align_bits >> 8) & 15), ldc, M, N, K, 0);
+    g.bias = (const bf16*)(at + ((align_bits >> 12) & 15));
+    if (has_residual) { g.R = (const bf16*)(at + ((align_bits >> 16) & 15)); g.ldr = ldr; g.res_mod = res_row_mod; }
+    g.out_f32 = out_f32;
+    bool staged = false;
+    const int tile = wg_gemm_decide(g, tile_hint, &staged);
+    return tile | (staged ? 64 : 0);
 }
 
 // Skinny rows, optionally with the LayerNorm in front and / or the weight matrix in fragment order:

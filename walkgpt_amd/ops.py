@@ -88,6 +88,28 @@ def gemm_tile_for(M, N, K, lda, ldw, ldc, ldr, tail_tiles=False):
     return _lib.lib().wg_gemm_pick_tile_mnk(M, N, K, 1 if tail_tiles else 0)
 
 
+GEMM_STAGED = 64  # flag bit of gemm_route's answer: the kernel runs the staged epilogue
+
+
+def gemm_route(x, weight, bias=None, residual=None, out=None, tile=0, tail_tiles=False, res_row_mod=0, out_f32=False):
+    """The kernel linear(x, weight, bias, residual=residual, out=out, tile=tile, tail_tiles=tail_tiles) launches for these tensors, by the
+    launcher's own decision (wg_gemm_route_of: shape, leading dimensions, pointer alignment, the fallbacks), + GEMM_STAGED when that
+    kernel runs the staged epilogue.  out None: a new contiguous tensor, fp32 with out_f32.  Launches nothing."""
+    _need_gpu(x, weight, bias, residual, out)
+    M, K, lda = _rows(x)
+    N = weight.shape[0]
+    ldc = N if out is None else _rows(out)[2]
+    f32 = out_f32 if out is None else out.dtype == torch.float32
+    ldr = _residual_ld(residual)
+    if tile == 0:
+        tile = gemm_tile_for(M, N, K, lda, weight.stride(0), ldc, ldr, tail_tiles)
+    bits = 0
+    for i, t in enumerate((x, weight, out, bias, residual)):
+        bits |= (_ptr(t) & 15) << (4 * i)
+    return _lib.lib().wg_gemm_route_of(M, N, K, lda, weight.stride(0), ldc, ldr, 0 if residual is None else 1, res_row_mod, 1 if f32 else 0,
+                                       bits, tile)
+
+
 def _forget_sidecars(t):
     """A caller-supplied `out=` tensor is about to be overwritten through its raw pointer (tensor._version does not move): whatever an
     earlier producer attached to it -- row partial sums, an e4m3 + block-scale copy -- no longer describes its contents."""
