@@ -527,3 +527,21 @@ def test_gemm_entry_points_refuse_bad_arguments_before_any_hip_call():
         if rc != -1 or not msg.startswith(prefix):
             bad.append((entry, spoil, rc, msg))
     assert bad == []
+
+
+def test_rows_hand_out_by_products_only_while_x_is_unedited():
+    """ops.Rows, the value that carries a GEMM's by-products to the next one: a fresh one hands them out, one whose x was edited in place
+    through torch hands out none, and nothing is ever stored on the tensor object itself."""
+    from walkgpt_amd import ops
+    x = torch.zeros(4, 256, dtype=torch.bfloat16)
+    part, pair = torch.zeros(1, 256, 2), (torch.zeros(4, 256, dtype=torch.uint8), torch.zeros(8, 256, dtype=torch.uint8))
+    r = ops.Rows(x, part, pair)
+    assert r.x is x and r.fresh() == (part, pair) and r.fresh()[0] is part and r.fresh()[1] is pair
+    assert ops.Rows(x).fresh() == (None, None)
+    assert not hasattr(r, "__dict__") and x.__dict__ == {}
+    r.x.add_(1)
+    assert r.fresh() == (None, None)
+    assert ops.Rows(x, part, pair).fresh() == (part, pair)          # made after the edit: describes the tensor as it is now
+    only_mx = ops.Rows(mx=pair)
+    assert only_mx.x is None and only_mx.partials is None and only_mx.fresh() == (None, pair)
+    assert x.__dict__ == {}

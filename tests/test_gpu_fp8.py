@@ -115,10 +115,10 @@ def test_quantize_mx_matches_the_stated_rule(dev, M, K, group):
     assert rel_err(_mx_deq(q, mx, M, group).cpu().numpy(), x.float().numpy()) < 0.04
     if K % 256 == 0:                                       # the chain-entry form: the same pass also leaves the rows' partial sums
         xd = x.to(dev)
-        q2, mx2 = ops.quantize_mx_fp8(xd, group=group, row_partials=True)
+        q2, mx2, part = ops.quantize_mx_fp8(xd, group=group, row_partials=True)
         idx = ops.mx_scale_index(M, dev, group)
         assert torch.equal(q2, q) and torch.equal(mx2[:, idx], mx[:, idx])
-        part = xd._wg_row_partials[0].cpu()[:, :M]
+        part = part.cpu()[:, :M]
         tiles = x.float().view(M, K // 256, 256)
         assert torch.allclose(part[..., 0].t(), tiles.sum(-1), rtol=1e-5, atol=1e-3)
         assert torch.allclose(part[..., 1].t(), (tiles * tiles).sum(-1), rtol=1e-5, atol=1e-3)
@@ -140,8 +140,8 @@ def test_attention_writes_its_output_as_the_mx_operand(dev, B, window, heads):
     o = ops.sam_attention(qkv, qb, rh, rw, B, grid, window, heads)
     q_ref, mx_ref = ops.quantize_mx_fp8(o)
     got = ops.sam_attention(qkv, qb, rh, rw, B, grid, window, heads, mx_out=True)
-    assert isinstance(got, tuple), "head_dim 64 with window 14 / global 64 x 64 carries the MX epilogue"
-    q, mx = got
+    assert got.mx is not None and got.x is None, "head_dim 64 with window 14 / global 64 x 64 carries the MX epilogue"
+    q, mx = got.mx
     idx = ops.mx_scale_index(M, dev, 128)
     assert torch.equal(mx[:, idx], mx_ref[:, idx])
     assert torch.equal(q, q_ref)
@@ -156,7 +156,7 @@ def test_attention_mx_epilogue_is_not_offered_at_head_dim_80(dev):
     qb = torch.zeros(3 * D, dtype=torch.bfloat16, device=dev)
     rh = torch.zeros(2 * window - 1, hd, dtype=torch.bfloat16, device=dev)
     out = ops.sam_attention(qkv, qb, rh, rh.clone(), B, grid, window, heads, mx_out=True)
-    assert not isinstance(out, tuple) and out.dtype == torch.bfloat16
+    assert out.mx is None and out.x.dtype == torch.bfloat16
 
 
 @pytest.mark.parametrize("M,N,K", [(256, 256, 128), (300, 264, 384), (1000, 520, 1280), (2100, 1032, 256)])
@@ -223,17 +223,19 @@ def test_mxfp8_transformer_block_chain(dev, M, D, H):
     eps = 1e-6
     x1 = ops.linear_mxfp8(ops.quantize_mx_fp8(o.to(dev)), ops.mx_weight(wp.to(dev)), bias=bp.to(dev), residual=x0.to(dev), mx_out=True, row_partials=True)
     # by-products of the producer: MX form and partial sums of exactly the bf16 values it stored
-    q_ref, s_ref = _mx_reference(x1.cpu())
-    xq, xm = x1._wg_mx
+    q_ref, s_ref = _mx_reference(x1.x.cpu())
+    xq, xm = x1.mx
     assert torch.equal(xm[:, ops.mx_scale_index(M, dev)].cpu(), s_ref) and torch.equal(xq.cpu(), q_ref)
-    part = x1._wg_row_partials[0].cpu()[:, :M]                                   # [D / 256, M, 2]
-    tiles = x1.float().cpu().view(M, D // 256, 256)
+    part = x1.partials.cpu()[:, :M]                                              # [D / 256, M, 2]
+    tiles = x1.x.float().cpu().view(M, D // 256, 256)
     assert torch.allclose(part[..., 0].t(), tiles.sum(-1), rtol=1e-5, atol=1e-3)
     assert torch.allclose(part[..., 1].t(), (tiles * tiles).sum(-1), rtol=1e-5, atol=1e-3)
     # LayerNorm folded into lin1, GELU, e4m3-only output
     fold = ops.fold_layernorm_mx(gam.to(dev), bet.to(dev), w1.to(dev), b1.to(dev))
-    hq, hm = ops.linear_mxfp8(x1, fold, act=1, ln_eps=eps, mx_out=True, bf16_out=False)
-    xf = x1.float().cpu()
+    h = ops.linear_mxfp8(x1, fold, act=1, ln_eps=eps, mx_out=True, bf16_out=False)
+    assert h.x is None
+    hq, hm = h.mx
+    xf = x1.x.float().cpu()
     mean, var = xf.mean(1, keepdim=True), xf.var(1, unbiased=False, keepdim=True)
     rstd = (var + eps).rsqrt()
     xd = _mx_deq(xq, xm, M, 128).cpu()
@@ -244,13 +246,13 @@ def test_mxfp8_transformer_block_chain(dev, M, D, H):
     h_full = torch.nn.functional.gelu(torch.nn.functional.layer_norm(xf, (D,), gam.float(), bet.float(), eps) @ w1.float().t() + b1.float())
     e_h = rel_err(hd.numpy(), h_full.numpy())
     # lin2 back onto the residual stream
-    x2 = ops.linear_mxfp8((hq, hm), ops.mx_weight(w2.to(dev)), bias=b2.to(dev), residual=x1, mx_out=True, row_partials=True)
+    x2 = ops.linear_mxfp8((hq, hm), ops.mx_weight(w2.to(dev)), bias=b2.to(dev), residual=x1.x, mx_out=True, row_partials=True)
     y_full = h_full @ w2.float().t() + b2.float() + xf
-    e_y = rel_err(x2.float().cpu().numpy(), y_full.numpy())
+    e_y = rel_err(x2.x.float().cpu().numpy(), y_full.numpy())
     print("mxfp8 block chain M=%d D=%d H=%d: hidden layer rel err vs fp32 %.4f, block output %.4f" % (M, D, H, e_h, e_y))
     assert e_h < 0.06 and e_y < 0.03
-    q2, s2 = _mx_reference(x2.cpu())
-    assert torch.equal(x2._wg_mx[1][:, ops.mx_scale_index(M, dev)].cpu(), s2) and torch.equal(x2._wg_mx[0].cpu(), q2)
+    q2, s2 = _mx_reference(x2.x.cpu())
+    assert torch.equal(x2.mx[1][:, ops.mx_scale_index(M, dev)].cpu(), s2) and torch.equal(x2.mx[0].cpu(), q2)
 
 
 @pytest.mark.parametrize("name", ["tiny", "vit_h3"])

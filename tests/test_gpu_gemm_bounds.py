@@ -228,10 +228,10 @@ def test_kernel_18_exact_output_and_partial_sums(dev, M, N, K):
     assert ops.gemm_route(ad, wd, bd, rdv, tile=16) == 16 | S
     with ops.time_gemms() as rec:
         y = ops.linear(ad, wd, bd, residual=rdv, row_partials=True)
-    assert [k for k, *_ in rec] == [18] and hasattr(y, "_wg_row_partials")
+    assert [k for k, *_ in rec] == [18] and y.partials is not None
     exp = gr.exact_expected(a, w, b, r, 0, gr.ACT_NONE, True, False)
-    assert torch.equal(y.cpu(), exp)
-    part, mpad = y._wg_row_partials[0], y._wg_row_partials[1]
+    assert torch.equal(y.x.cpu(), exp)
+    part, mpad = y.partials, y.partials.shape[1]
     assert part.shape == (N // 256, mpad, 2) and mpad == (M + 255) // 256 * 256
     yt = exp.double().view(M, N // 256, 256)
     assert (yt * yt).sum(-1).max().item() < 2 ** 24 and yt.abs().sum(-1).max().item() < 2 ** 24
@@ -250,14 +250,14 @@ def test_kernel_17_fed_by_18s_partial_sums_under_the_bound(dev, M, D, N2):
     w = (torch.randn(D, Kp, generator=g) / Kp ** 0.5).to(torch.bfloat16)
     r = (torch.randn(M, D, generator=g) * (0.5 + torch.rand(M, 1, generator=g)) + 3.0 * torch.randn(M, 1, generator=g)).to(torch.bfloat16)
     y = ops.linear(x.to(dev), w.to(dev), residual=r.to(dev), row_partials=True)
-    assert hasattr(y, "_wg_row_partials") and y._wg_row_partials[0].shape[0] == D // 256
+    assert y.partials is not None and y.partials.shape[0] == D // 256
     gamma = (1.0 + 0.3 * torch.randn(D, generator=g)).to(torch.bfloat16)
     beta = (0.2 * torch.randn(D, generator=g)).to(torch.bfloat16)
     w2 = (torch.randn(N2, D, generator=g) / D ** 0.5).to(torch.bfloat16)
     b2 = torch.randn(N2, generator=g).to(torch.bfloat16)
     fold = ops.fold_layernorm(gamma.to(dev), beta.to(dev), w2.to(dev), b2.to(dev))
-    assert ops.gemm_route(y, fold["wg"], tile=16) == 16 | S
-    yc, wg, cs, bf = y.cpu(), fold["wg"].cpu(), fold["colsum"].cpu(), fold["bias_f32"].cpu()
+    assert ops.gemm_route(y.x, fold["wg"], tile=16) == 16 | S
+    yc, wg, cs, bf = y.x.cpu(), fold["wg"].cpu(), fold["colsum"].cpu(), fold["bias_f32"].cpu()
     st = gr.row_stats64(yc, eps)
     prod = gr.ln_products(yc, wg)
     for act in (gr.ACT_NONE, gr.ACT_GELU):

@@ -245,12 +245,12 @@ def test_row_partials_travel_from_gemm_to_ln_gemm(dev, M, N, K, Kn):
     r = (torch.randn(M, N, generator=g) * (0.5 + torch.rand(M, 1, generator=g)) + 3.0 * torch.randn(M, 1, generator=g)).to(torch.bfloat16)
     xd, wd, bd, rd = x.to(dev), w.to(dev), b.to(dev), r.to(dev)
     y = ops.linear(xd, wd, bd, residual=rd, row_partials=True)
-    assert hasattr(y, "_wg_row_partials"), "the shape must take the statistics-producing kernel"
+    assert y.partials is not None, "the shape must take the statistics-producing kernel"
     plain = ops.linear(xd, wd, bd, residual=rd)
-    assert torch.equal(y, plain)                                     # same arithmetic, same stores
-    part, mpad = y._wg_row_partials[0], y._wg_row_partials[1]
+    assert torch.equal(y.x, plain)                                   # same arithmetic, same stores
+    part, mpad = y.partials, y.partials.shape[1]
     assert part.shape == (N // 256, mpad, 2) and mpad % 256 == 0 and mpad >= M
-    yt = y.float().view(M, N // 256, 256)
+    yt = y.x.float().view(M, N // 256, 256)
     assert torch.allclose(part[:, :M, 0].t(), yt.sum(-1), rtol=1e-5, atol=1e-3)
     assert torch.allclose(part[:, :M, 1].t(), (yt * yt).sum(-1), rtol=1e-5, atol=1e-3)
     # consumer: the same LayerNorm-folded GEMM with statistics from the partial sums / from the statistics pass / in fp32 torch
@@ -262,18 +262,17 @@ def test_row_partials_travel_from_gemm_to_ln_gemm(dev, M, N, K, Kn):
     with ops.time_gemms() as rec:
         got = ops.ln_linear(y, fold, 1e-6, act=ops.ACT_GELU)
     assert [k for k, *_ in rec] == [17]                              # one launch: no row-statistics pass, no two-kernel route
-    ref = _ref_act(torch.nn.functional.linear(torch.nn.functional.layer_norm(y.float().cpu(), (N,), gamma.float(), beta.float(), 1e-6),
+    ref = _ref_act(torch.nn.functional.linear(torch.nn.functional.layer_norm(y.x.float().cpu(), (N,), gamma.float(), beta.float(), 1e-6),
                                               w2.float(), b2.float()), ops.ACT_GELU)
     err = (got.float().cpu() - ref).abs().max().item()
     assert err <= 0.03 * max(1.0, ref.abs().max().item()), err
     via_pass = ops.ln_linear(plain, fold, 1e-6, act=ops.ACT_GELU)      # `plain` carries no partial sums: statistics pass + GEMM
     d = (got.float() - via_pass.float()).abs().max().item()
     assert d <= 0.02 * max(1.0, ref.abs().max().item()), d
-    # a view or an in-place edit drops the hand-over instead of using stale sums
-    y2 = y.clone()
-    y2._wg_row_partials = y._wg_row_partials[:2] + (y2._version,) + y._wg_row_partials[3:]
-    y2.mul_(2.0)
-    assert torch.equal(ops.ln_linear(y2, fold, 1e-6), ops.ln_linear(y2.clone(), fold, 1e-6))
+    # an in-place edit drops the hand-over instead of using stale sums
+    y2 = ops.Rows(y.x.clone(), y.partials)
+    y2.x.mul_(2.0)
+    assert torch.equal(ops.ln_linear(y2, fold, 1e-6), ops.ln_linear(y2.x.clone(), fold, 1e-6))
 
 
 def test_row_partials_are_refused_for_shapes_the_kernel_cannot_take(dev):
@@ -284,9 +283,9 @@ def test_row_partials_are_refused_for_shapes_the_kernel_cannot_take(dev):
     x = torch.randn(64, 64, device=dev).to(torch.bfloat16)
     w = torch.randn(256, 64, device=dev).to(torch.bfloat16)
     y = ops.linear(x, w, row_partials=True)                                            # too few rows for the persistent kernel: plain GEMM
-    assert not hasattr(y, "_wg_row_partials")
+    assert y.partials is None
     part = torch.empty(1, 256, 2, device=dev)
-    rc = L.wg_gemm_bias_act_stats_bf16(x.data_ptr(), 64, w.data_ptr(), 64, None, None, 0, 0, y.data_ptr(), 256, 64, 256, 64, 0, part.data_ptr(), 256, None)
+    rc = L.wg_gemm_bias_act_stats_bf16(x.data_ptr(), 64, w.data_ptr(), 64, None, None, 0, 0, y.x.data_ptr(), 256, 64, 256, 64, 0, part.data_ptr(), 256, None)
     assert rc != 0 and b"persistent" in L.wg_last_error()
 
 

@@ -1,0 +1,101 @@
+"""The hand-over of a GEMM's by-products (ops.Rows: row partial sums, the e4m3 copy) through a whole encoder, bf16 and fp8: which GEMM
+kernels are launched, in which order, and how many statistics / quantisation passes run beside them.  The golden encoders are too narrow
+or have too few rows for the persistent kernel; these two are the smallest that reach it (D = 256: 64 tiles of 256 x 256 at M = 16384)."""
+from functools import partial
+from types import SimpleNamespace
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from walkgpt_amd import ops
+from walkgpt_amd.clip_encoder import _CLIPVisionTransformer
+from walkgpt_amd.segment_anything.modeling import ImageEncoderViT
+
+D, HIDDEN = 256, 1024
+
+
+def _assert_chain_shapes_take_the_persistent_kernel(M, producers_k):
+    """Every residual-stream GEMM (N = D; K as listed) leaves row partials and both LayerNorm-folded GEMMs take the one-launch route."""
+    L = ops._lib.lib()
+    for K in producers_k:
+        assert L.wg_gemm_row_partials_supported(M, D, K, K, K, D) == 1, (M, D, K)
+    for N in (3 * D, HIDDEN):
+        assert L.wg_gemm_ln_supported(M, N, D, D, D, N) == 1, (M, N, D)
+
+
+def _run_counted(fn):
+    """fn() under time_gemms with ops.row_stats / ops.quantize_mx_fp8 counted -> (kernel ids, row_stats calls, quantize_mx_fp8 kwargs)."""
+    counts = {"row_stats": [], "quantize_mx_fp8": []}
+    originals = {k: getattr(ops, k) for k in counts}
+
+    def counting(name):
+        def wrapper(*a, **kw):
+            counts[name].append(kw)
+            return originals[name](*a, **kw)
+        return wrapper
+
+    for k in counts:
+        setattr(ops, k, counting(k))
+    try:
+        with torch.no_grad(), ops.time_gemms() as rec:
+            out = fn()
+        torch.cuda.synchronize()
+    finally:
+        for k, f in originals.items():
+            setattr(ops, k, f)
+    assert all(torch.isfinite(o.float()).all() for o in out)
+    return [r[0] for r in rec], len(counts["row_stats"]), counts["quantize_mx_fp8"]
+
+
+@pytest.fixture(scope="module")
+def sam_encoder(dev):
+    torch.manual_seed(11)
+    enc = ImageEncoderViT(img_size=1024, patch_size=16, embed_dim=D, depth=2, num_heads=4, mlp_ratio=4, norm_layer=partial(torch.nn.LayerNorm, eps=1e-6),
+                          qkv_bias=True, use_rel_pos=True, global_attn_indexes=(1,), window_size=14, out_chans=256)
+    return enc.to(dev).bfloat16().eval()
+
+
+@pytest.fixture(scope="module")
+def clip_transformer(dev):
+    torch.manual_seed(21)
+    cfg = SimpleNamespace(hidden_size=D, intermediate_size=HIDDEN, num_hidden_layers=2, num_attention_heads=4, image_size=448, patch_size=14,
+                          layer_norm_eps=1e-5)
+    return _CLIPVisionTransformer(cfg).to(dev).bfloat16().eval()
+
+
+# Expected lists and counts: recorded from the commit before ops.Rows existed (by-products as tensor attributes), same encoders.
+@pytest.mark.parametrize("gemm_dtype,ids,row_stats,quantize", [
+    ("bf16", [18, 17, 18, 17, 18, 17, 18, 17, 18, 16, 16], 0, []),
+    # fp8: the patch-embedding GEMM (18) already left the partial sums, so the chain entry quantises without them; the attention
+    # kernels write the proj GEMM's MX operand themselves (head_dim 64)
+    ("fp8", [18, 22, 23, 22, 23, 22, 23, 22, 23, 16, 16], 0, [{"row_partials": False}]),
+])
+def test_sam_encoder_hands_by_products_from_gemm_to_gemm(dev, sam_encoder, gemm_dtype, ids, row_stats, quantize):
+    B, g = 4, 64
+    M = B * g * g                                       # 16384 x 256: exactly 64 tiles, the fewest the persistent kernel is picked for
+    _assert_chain_shapes_take_the_persistent_kernel(M, (768, D, HIDDEN))                    # patch embedding, proj, lin2
+    for blk in sam_encoder.blocks:
+        blk.gemm_dtype = gemm_dtype
+    sam_encoder.prepare()                               # derived (folded / quantised) weights first: the counts are the forward's own
+    x = torch.randn(B, 3, 1024, 1024, device=dev, generator=torch.Generator(dev).manual_seed(12)).to(torch.bfloat16)
+    got = _run_counted(lambda: [sam_encoder.forward_tokens(x)])
+    assert got == (ids, row_stats, quantize)
+
+
+@pytest.mark.parametrize("gemm_dtype,ids,row_stats,quantize", [
+    # 16 patch-embedding GEMMs (one per image, written behind its class token); layer 0 has no producing GEMM in front: one statistics pass
+    ("bf16", [11] * 16 + [17, 18, 17, 18, 17, 18, 17, 18], 1, []),
+    # fp8: the entry quantisation also makes the partial sums; the attention output is quantised once per layer
+    ("fp8", [11] * 16 + [22, 23, 22, 23, 22, 23, 22, 23], 0, [{"row_partials": True}, {}, {}]),
+])
+def test_clip_encoder_hands_by_products_from_gemm_to_gemm(dev, clip_transformer, gemm_dtype, ids, row_stats, quantize):
+    B, tokens = 16, 1025
+    _assert_chain_shapes_take_the_persistent_kernel(B * tokens, (D, HIDDEN))                # out_proj, fc2
+    for layer in clip_transformer.encoder.layers:
+        layer.gemm_dtype = gemm_dtype
+        layer._prep_get(layer._build) if gemm_dtype == "bf16" else layer._prep_get(layer._build_mx, slot="_mx")
+    x = torch.randn(B, 3, 448, 448, device=dev, generator=torch.Generator(dev).manual_seed(22)).to(torch.bfloat16)
+    got = _run_counted(lambda: list(clip_transformer.hidden_states(x, None, [0, 1, 2]).values()))
+    assert got == (ids, row_stats, quantize)

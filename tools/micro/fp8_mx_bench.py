@@ -33,14 +33,14 @@ for (M, D, H) in [(32768, 1280, 5120), (32768, 768, 3072), (8200, 1024, 4096)]:
     w1 = (torch.randn(H, D, device=dev) / D ** 0.5).bfloat16(); w2 = (torch.randn(D, H, device=dev) / H ** 0.5).bfloat16()
     b1 = torch.randn(H, device=dev).bfloat16(); b2 = torch.randn(D, device=dev).bfloat16()
     g = torch.ones(D, device=dev).bfloat16(); be = torch.zeros(D, device=dev).bfloat16()
-    ops.mx_prepare_rows(x)
+    x = ops.mx_rows(x)
     f1 = ops.fold_layernorm_mx(g, be, w1, b1); wd2 = ops.mx_weight(w2); wd1 = ops.mx_weight(w1)
     h = ops.linear_mxfp8(x, f1, act=1, ln_eps=1e-6, mx_out=True, bf16_out=False)
     fl = 2.0 * M * D * H
-    a = t(lambda: ops.linear_mxfp8(x._wg_mx, wd1, bias=b1))
-    b = t(lambda: ops.linear_mxfp8(x._wg_mx, wd1, bias=b1, act=1))
+    a = t(lambda: ops.linear_mxfp8(x.mx, wd1, bias=b1))
+    b = t(lambda: ops.linear_mxfp8(x.mx, wd1, bias=b1, act=1))
     c = t(lambda: ops.linear_mxfp8(x, f1, act=1, ln_eps=1e-6, mx_out=True, bf16_out=False))
-    d = t(lambda: ops.linear_mxfp8(h, wd2, bias=b2, residual=x))
-    e = t(lambda: ops.linear_mxfp8(h, wd2, bias=b2, residual=x, mx_out=True, row_partials=True))
+    d = t(lambda: ops.linear_mxfp8(h, wd2, bias=b2, residual=x.x))
+    e = t(lambda: ops.linear_mxfp8(h, wd2, bias=b2, residual=x.x, mx_out=True, row_partials=True))
     print("M=%d D=%d H=%d: lin1 plain %.1f us (%.0f TF/s) | + GELU %.1f (%.0f) | LN fold + GELU + e4m3 out %.1f (%.0f) || lin2 + residual %.1f (%.0f) | + e4m3 copy + partials %.1f (%.0f)"
           % (M, D, H, a, fl / a / 1e6, b, fl / b / 1e6, c, fl / c / 1e6, d, fl / d / 1e6, e, fl / e / 1e6), flush=True)

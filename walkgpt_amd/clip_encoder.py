@@ -91,30 +91,27 @@ class _EncoderLayer(nn.Module, _Prepared):
         return {"qkv": ops.fold_layernorm_mx(n1.weight, n1.bias, w, b), "out": ops.mx_weight(a.out_proj.weight),
                 "fc1": ops.fold_layernorm_mx(n2.weight, n2.bias, m.fc1.weight, m.fc1.bias), "fc2": ops.mx_weight(m.fc2.weight)}
 
-    def run_mx(self, x, key_bias):
+    def run_mx(self, r, key_bias):
         """The layer as one MX chain on the persistent fp8 GEMM (as Block.rows_mx of the SAM encoder)."""
         a, m = self.self_attn, self.mlp
         w = self._prep_get(self._build_mx, slot="_mx")
-        D = x.shape[-1]
-        qkv = ops.linear_mxfp8(x, w["qkv"], ln_eps=self.layer_norm1.eps)
+        D = r.x.shape[-1]
+        qkv = ops.linear_mxfp8(r, w["qkv"], ln_eps=self.layer_norm1.eps)
         o = ops.mha(qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:], a.num_heads, a.scale, key_bias, small=False)
-        x = ops.linear_mxfp8(ops.quantize_mx_fp8(o), w["out"], bias=a.out_proj.bias, residual=x, mx_out=True, row_partials=True)
-        h = ops.linear_mxfp8(x, w["fc1"], act=ops.ACT_QUICK_GELU, ln_eps=self.layer_norm2.eps, mx_out=True, bf16_out=False)
-        return ops.linear_mxfp8(h, w["fc2"], bias=m.fc2.bias, residual=x, mx_out=True, row_partials=True)
+        r = ops.linear_mxfp8(ops.quantize_mx_fp8(o), w["out"], bias=a.out_proj.bias, residual=r.x, mx_out=True, row_partials=True)
+        h = ops.linear_mxfp8(r, w["fc1"], act=ops.ACT_QUICK_GELU, ln_eps=self.layer_norm2.eps, mx_out=True, bf16_out=False)
+        return ops.linear_mxfp8(h, w["fc2"], bias=m.fc2.bias, residual=r.x, mx_out=True, row_partials=True)
 
-    def run_fp8(self, x, key_bias):
+    def run_fp8(self, r, key_bias):
         """The layer on the fp8 GEMM path (as Block.rows_fp8 of the SAM encoder): the MX chain where the widths allow it, otherwise per-row
         activation scales with both LayerNorms fused into the quantisation of their output.  Attention, the residual stream and every
         statistic stay bf16 / fp32."""
         a, m = self.self_attn, self.mlp
-        if ops.mx_chain_ok(x.shape[-1], m.fc1.weight.shape[0]) and ops.mx_prepare_rows(x):
-            return self.run_mx(x, key_bias)
-        key = tuple((p.data_ptr(), p._version) for p in (a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, a.out_proj.weight, m.fc1.weight,
-                                                         m.fc2.weight, a.q_proj.bias, a.k_proj.bias, a.v_proj.bias))
-        w = self.__dict__.get("_fp8_val")
-        if w is None or self.__dict__.get("_fp8_key") != key:
-            w = self._build_fp8()
-            self.__dict__["_fp8_val"], self.__dict__["_fp8_key"] = w, key
+        x = r.x
+        if ops.mx_chain_ok(x.shape[-1], m.fc1.weight.shape[0]):
+            return self.run_mx(ops.mx_rows(r), key_bias)
+        w = self._prep_get(self._build_fp8, (a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, a.out_proj.weight, m.fc1.weight, m.fc2.weight,
+                                             a.q_proj.bias, a.k_proj.bias, a.v_proj.bias), slot="_fp8")
         D = x.shape[-1]
         q, s = ops.quantize_rows_fp8(x, ln=(self.layer_norm1.weight, self.layer_norm1.bias), eps=self.layer_norm1.eps)
         qkv = ops.linear_fp8(q, s, *w["qkv"], bias=w["bqkv"])
@@ -123,22 +120,22 @@ class _EncoderLayer(nn.Module, _Prepared):
         x = ops.linear_fp8(q, s, *w["out"], bias=a.out_proj.bias, residual=x)
         q, s = ops.quantize_rows_fp8(x, ln=(self.layer_norm2.weight, self.layer_norm2.bias), eps=self.layer_norm2.eps)
         q, s = ops.quantize_rows_fp8(ops.linear_fp8(q, s, *w["fc1"], bias=m.fc1.bias, act=ops.ACT_QUICK_GELU))
-        return ops.linear_fp8(q, s, *w["fc2"], bias=m.fc2.bias, residual=x)
+        return ops.Rows(ops.linear_fp8(q, s, *w["fc2"], bias=m.fc2.bias, residual=x))
 
-    def run(self, x, key_bias, tail_tiles=False):
-        """HF CLIPEncoderLayer: pre-LN attention + pre-LN quick-GELU MLP, both residual.  x [B, L, D].
+    def run(self, r, key_bias, tail_tiles=False):
+        """HF CLIPEncoderLayer: pre-LN attention + pre-LN quick-GELU MLP, both residual.  r: ops.Rows of x [B, L, D] -> the same of the output.
         Both LayerNorms are folded into the GEMM behind them (ops.ln_linear).  tail_tiles: let the M = B*1025 GEMMs use the
         tail-absorbing tiles (faster when nothing else shares the GPU, slower under stream overlap)."""
         if self.gemm_dtype == "fp8":
-            return self.run_fp8(x, key_bias)
+            return self.run_fp8(r, key_bias)
         a = self.self_attn
         p = self._prep_get(self._build)
-        D = x.shape[-1]
-        qkv = ops.ln_linear(x, p["qkv"], self.layer_norm1.eps, tail_tiles=tail_tiles)
+        D = r.x.shape[-1]
+        qkv = ops.ln_linear(r, p["qkv"], self.layer_norm1.eps, tail_tiles=tail_tiles)
         o = ops.mha(qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:], a.num_heads, a.scale, key_bias, small=False)
-        x = ops.linear(o, a.out_proj.weight, a.out_proj.bias, residual=x, tail_tiles=tail_tiles, row_partials=True)
-        h = ops.ln_linear(x, p["fc1"], self.layer_norm2.eps, act=ops.ACT_QUICK_GELU, tail_tiles=tail_tiles)
-        return ops.linear(h, self.mlp.fc2.weight, self.mlp.fc2.bias, residual=x, tail_tiles=tail_tiles, row_partials=True)
+        r = ops.linear(o, a.out_proj.weight, a.out_proj.bias, residual=r.x, tail_tiles=tail_tiles, row_partials=True)
+        h = ops.ln_linear(r, p["fc1"], self.layer_norm2.eps, act=ops.ACT_QUICK_GELU, tail_tiles=tail_tiles)
+        return ops.linear(h, self.mlp.fc2.weight, self.mlp.fc2.bias, residual=r.x, tail_tiles=tail_tiles, row_partials=True)
 
 
 class _Encoder(nn.Module):
@@ -182,18 +179,18 @@ class _CLIPVisionTransformer(nn.Module, _Prepared):
         for b in range(B):  # rows of image b land directly behind its class token
             ops.linear(rows[b * P:(b + 1) * P], p["patch_w"], residual=pos[1:], out=x[b, 1:])
         x[:, 0] = ops.add_rows(e.class_embedding.reshape(1, D), pos[:1])
-        x = ops.layernorm(x, self.pre_layrnorm.weight, self.pre_layrnorm.bias, self.pre_layrnorm.eps)
+        r = ops.Rows(ops.layernorm(x, self.pre_layrnorm.weight, self.pre_layrnorm.bias, self.pre_layrnorm.eps))
         key_bias = None
         if attention_mask is not None:  # custom_clip.py:27-38: (1 - mask) * finfo.min on padded keys
             key_bias = torch.where(attention_mask > 0.5, 0.0, torch.finfo(torch.float32).min).float().contiguous()
         n = len(self.encoder.layers)
         idx = {(i if i >= 0 else n + 1 + i) for i in want}
-        keep = {0: x} if 0 in idx else {}
+        keep = {0: r.x} if 0 in idx else {}     # the bf16 tensors alone: a kept state does not hold on to its by-products
         last = n if run_all_layers else max(idx)
         for i in range(last):
-            x = self.encoder.layers[i].run(x, key_bias, tail_tiles)
+            r = self.encoder.layers[i].run(r, key_bias, tail_tiles)
             if i + 1 in idx:
-                keep[i + 1] = x
+                keep[i + 1] = r.x
         return {w_: keep[w_ if w_ >= 0 else n + 1 + w_] for w_ in want}
 
 

@@ -110,21 +110,29 @@ def gemm_route(x, weight, bias=None, residual=None, out=None, tile=0, tail_tiles
                                        bits, tile)
 
 
-def _forget_sidecars(t):
-    """A caller-supplied `out=` tensor is about to be overwritten through its raw pointer (tensor._version does not move): whatever an
-    earlier producer attached to it -- row partial sums, an e4m3 + block-scale copy -- no longer describes its contents."""
-    if t is not None:
-        for a in ("_wg_row_partials", "_wg_mx"):
-            if hasattr(t, a):
-                delattr(t, a)
+class Rows:
+    """Activation rows on their way from one GEMM to the next, with the by-products the producing kernel left beside them:
+    x         bf16 [..., D]; None where only the fp8 form exists (the MLP hidden layer of the MX chain);
+    partials  fp32 [D / 256, mpad, 2], the rows' {sum, sum of squares} per 256-column tile (mpad: rows padded to whole tiles), or None;
+    mx        (e4m3 bytes [..., D], E8M0 block-scale planes [D / 32, mx_pitch(rows)]), or None.
+    A Rows is a value: its x is not written after the Rows is made.  A torch in-place edit of x moves x._version, and fresh() then hands
+    out neither by-product (the consumer runs its own pass); a write through x's raw pointer -- any wrapper's `out=` -- cannot be seen."""
+    __slots__ = ("x", "partials", "mx", "_version")
+
+    def __init__(self, x=None, partials=None, mx=None):
+        self.x, self.partials, self.mx = x, partials, mx
+        self._version = None if x is None else x._version
+
+    def fresh(self):
+        """(partials, mx) while x is as it was when they were made, else (None, None)."""
+        if self.x is not None and self.x._version != self._version:
+            return None, None
+        return self.partials, self.mx
 
 
 def _out(out, x, N, dtype=_BF16):
-    """The result tensor [..., N] of a GEMM on rows x: the caller's `out` (minus what earlier producers attached to it), else a new one."""
-    _forget_sidecars(out)
-    if out is None:
-        out = torch.empty(x.shape[:-1] + (N,), device=x.device, dtype=dtype)
-    return out
+    """The result tensor [..., N] of a GEMM on rows x: the caller's `out`, else a new one."""
+    return torch.empty(x.shape[:-1] + (N,), device=x.device, dtype=dtype) if out is None else out
 
 
 def _residual_ld(residual):
@@ -138,9 +146,9 @@ def _residual_ld(residual):
 def linear(x, weight, bias=None, act=ACT_NONE, residual=None, res_row_mod=0, out=None, out_f32=False, tile=0, tail_tiles=False,
            row_partials=False):
     """y = act(x @ weight.T + bias) (+ residual).  x [..., K] bf16, weight [N, K] bf16.
-    row_partials: y feeds a LayerNorm that ln_linear folds into the next GEMM -- where the shape allows it the GEMM also leaves the
-    per-row partial sums of y (wg_gemm_bias_act_stats_bf16) and ln_linear(y, ...) picks them up instead of running a statistics
-    pass (they ride on the returned tensor object: a view or an in-place edit of y silently falls back to the pass)."""
+    row_partials: y feeds a LayerNorm that ln_linear folds into the next GEMM -- the result is a Rows; where the shape allows it the
+    GEMM also leaves the per-row partial sums of y in it (wg_gemm_bias_act_stats_bf16) and ln_linear(rows, ...) reads them instead of
+    running a statistics pass (partials None: the shape does not take that kernel)."""
     _need_gpu(x, weight, bias, residual, out)
     assert x.dtype == _BF16 and weight.dtype == _BF16
     M, K, lda = _rows(x)
@@ -162,8 +170,7 @@ def linear(x, weight, bias=None, act=ACT_NONE, residual=None, res_row_mod=0, out
         rc = _lib.lib().wg_gemm_bias_act_stats_bf16(x.data_ptr(), lda, weight.data_ptr(), weight.stride(0), _ptr(bias), _ptr(residual), ldr,
                                                     res_row_mod, out.data_ptr(), ldc, M, N, K, act, part.data_ptr(), mpad, _stream())
         _checked(ev, rc, "wg_gemm_bias_act_stats_bf16")
-        out._wg_row_partials = (part, mpad, out._version, M, N)
-        return out
+        return Rows(out, part)
     if tile == 0:
         tile = gemm_tile_for(M, N, K, lda, weight.stride(0), ldc, ldr, tail_tiles)
     ev = _timed(tile, M, N, K)
@@ -171,14 +178,13 @@ def linear(x, weight, bias=None, act=ACT_NONE, residual=None, res_row_mod=0, out
                                           _ptr(residual), ldr, res_row_mod, out.data_ptr(), ldc, M, N, K, act,
                                           1 if out.dtype == torch.float32 else 0, tile, _stream())
     _checked(ev, rc, "wg_gemm_bias_act_bf16")
-    return out
+    return Rows(out) if row_partials else out
 
 
 def layernorm(x, gamma, beta, eps, act=ACT_NONE, out=None):
     _need_gpu(x, gamma, beta, out)
     assert x.dtype == _BF16 and gamma.dtype == _BF16 and beta.dtype == _BF16
     M, D, ldx = _rows(x)
-    _forget_sidecars(out)
     if out is None:
         out = torch.empty(x.shape, device=x.device, dtype=_BF16)
     _, _, ldy = _rows(out)
@@ -211,8 +217,12 @@ def row_stats(x, eps):
 
 
 def ln_linear(x, fold, eps, act=ACT_NONE, tail_tiles=False):
-    """act(LayerNorm(x) @ W.T + b) with `fold` from fold_layernorm.  Shapes the persistent 256x256 GEMM takes run as a
-    row-statistics pass + one GEMM on the raw rows (the normalised rows never reach HBM); the rest as LayerNorm + GEMM."""
+    """act(LayerNorm(x) @ W.T + b) with `fold` from fold_layernorm; x a tensor or a Rows.  Shapes the persistent 256x256 GEMM takes run
+    as one GEMM on the raw rows (the normalised rows never reach HBM), on the Rows' partial sums where it has fresh ones and behind a
+    row-statistics pass otherwise; the rest as LayerNorm + GEMM."""
+    part = None
+    if isinstance(x, Rows):
+        part, x = x.fresh()[0], x.x
     _need_gpu(x)
     assert x.dtype == _BF16
     M, K, lda = _rows(x)
@@ -221,13 +231,12 @@ def ln_linear(x, fold, eps, act=ACT_NONE, tail_tiles=False):
     if not L.wg_gemm_ln_supported(M, N, K, lda, K, N):
         return linear(layernorm(x, fold["gamma"], fold["beta"], eps), fold["weight"], fold["bias"], act=act, tail_tiles=tail_tiles)
     out = torch.empty(x.shape[:-1] + (N,), device=x.device, dtype=_BF16)
-    rp = getattr(x, "_wg_row_partials", None)
-    if rp is not None and rp[2] == x._version and rp[3] == M and rp[4] == K:
+    if part is not None:
         # the GEMM that wrote x left its rows' partial sums (linear(..., row_partials=True)): no statistics pass
-        part, mpad = rp[0], rp[1]
+        assert part.shape[0] * 256 == K and part.shape[1] >= M
         ev = _timed(17, M, N, K)
         rc = L.wg_gemm_lnp_bias_act_bf16(x.data_ptr(), lda, fold["wg"].data_ptr(), K, fold["bias_f32"].data_ptr(), fold["colsum"].data_ptr(),
-                                         part.data_ptr(), part.shape[0], mpad, float(eps), out.data_ptr(), N, M, N, K, act, _stream())
+                                         part.data_ptr(), part.shape[0], part.shape[1], float(eps), out.data_ptr(), N, M, N, K, act, _stream())
         _checked(ev, rc, "wg_gemm_lnp_bias_act_bf16")
         return out
     st = row_stats(x, eps)
@@ -312,7 +321,6 @@ def mha(q, k, v, heads, scale, key_bias=None, out=None, small=None):
     assert kbs == vbs
     D = q.shape[2]
     hd = D // heads
-    _forget_sidecars(out)
     if out is None:
         out = torch.empty(B, Lq, D, device=q.device, dtype=_BF16)
     _, _, ldo, obs = _rows_per_batch(out)
@@ -332,9 +340,9 @@ def mha(q, k, v, heads, scale, key_bias=None, out=None, small=None):
 
 def sam_attention(qkv, qkv_bias, rel_pos_h, rel_pos_w, B, grid, window, heads, out=None, mx_out=False):
     """SAM ViT attention over packed qkv rows [B*grid*grid, 3D]; window == grid means global attention.
-    mx_out: the fp8 chain's form -- where the kernels carry it (head_dim 64; window 14 or the 64 x 64 global grid) the result is the tuple
-    (e4m3 bytes, E8M0 block scales) quantize_mx_fp8 would make of the bf16 output, written by the attention kernel itself; elsewhere the bf16
-    tensor as usual (the caller quantises)."""
+    mx_out: the fp8 chain's form, a Rows -- where the kernels carry it (head_dim 64; window 14 or the 64 x 64 global grid) with mx alone:
+    the (e4m3 bytes, E8M0 block scales) quantize_mx_fp8 would make of the bf16 output, written by the attention kernel itself; elsewhere
+    with x alone, the bf16 tensor as usual (the caller quantises)."""
     _need_gpu(qkv, qkv_bias, rel_pos_h, rel_pos_w, out)
     D = qkv.shape[-1] // 3
     hd = D // heads
@@ -347,15 +355,14 @@ def sam_attention(qkv, qkv_bias, rel_pos_h, rel_pos_w, B, grid, window, heads, o
         rc = _lib.lib().wg_sam_attn_relpos_mx_bf16(qkv.data_ptr(), qkv_bias.data_ptr(), rel_pos_h.data_ptr(), rel_pos_w.data_ptr(), q.data_ptr(), mx.data_ptr(),
                                                    mx.shape[1], B, grid, window, heads, hd, float(hd) ** -0.5, _stream())
         _lib.check(rc, "wg_sam_attn_relpos_mx_bf16")
-        return q, mx
-    _forget_sidecars(out)
+        return Rows(mx=(q, mx))
     if out is None:
         out = torch.empty(B * grid * grid, D, device=qkv.device, dtype=_BF16)
     rc = _lib.lib().wg_sam_attn_relpos_bf16(qkv.data_ptr(), qkv_bias.data_ptr(), rel_pos_h.data_ptr(),
                                             rel_pos_w.data_ptr(), out.data_ptr(), B, grid, window, heads, hd,
                                             float(hd) ** -0.5, _stream())
     _lib.check(rc, "wg_sam_attn_relpos_bf16")
-    return out
+    return Rows(out) if mx_out else out
 
 
 def patchify(images, patch, kpad=None):
@@ -387,7 +394,6 @@ def add_rows(a, b, out=None):
     rows, cols, lda = _rows(a)
     rb, cb, ldb = _rows(b)
     assert cb == cols
-    _forget_sidecars(out)
     if out is None:
         out = torch.empty(a.shape, device=a.device, dtype=_BF16)
     _, _, ldo = _rows(out)
@@ -540,7 +546,7 @@ def mx_scale_index(M, device=None, group=128):
 def quantize_mx_fp8(x, group=128, row_partials=False):
     """x [..., K] bf16 -> (e4m3 bytes uint8 [..., K], E8M0 block scales uint8 [K / 32, mx_pitch(rows)]): OCP-MX, one power-of-two scale per
     (row, 32 columns).  group=128: an activation operand of linear_mxfp8; group=64: its weight operand (once per weight).
-    row_partials (K % 256 == 0): the same pass also attaches x's row partial sums (x._wg_row_partials), as a GEMM epilogue would have."""
+    row_partials (K % 256 == 0): the same pass also makes x's row partial sums, as a GEMM epilogue would have, and returns them third."""
     _need_gpu(x)
     assert x.dtype == _BF16
     M, K, ldx = _rows(x)
@@ -550,9 +556,7 @@ def quantize_mx_fp8(x, group=128, row_partials=False):
     rc = _lib.lib().wg_quantize_mx_fp8(x.data_ptr(), ldx, q.data_ptr(), K, mx.data_ptr(), mx.shape[1], group, M, K, _ptr(part),
                                        part.shape[1] if row_partials else 0, _stream())
     _lib.check(rc, "wg_quantize_mx_fp8")
-    if row_partials:
-        x._wg_row_partials = (part, part.shape[1], x._version, M, K)
-    return q, mx
+    return (q, mx, part) if row_partials else (q, mx)
 
 
 def mx_dequantize(q, mx, group=128):
@@ -585,33 +589,35 @@ def mx_chain_ok(D, hidden):
     return D % 256 == 0 and D <= 1280 and hidden % 32 == 0 and hidden % 128 == 0
 
 
-def mx_prepare_rows(x):
-    """Give a bf16 activation tensor [.., D] (D % 256 == 0) the by-products an MX-chain consumer (linear_mxfp8(ln_eps=...)) expects: its
-    e4m3 + block-scale form and its rows' partial sums.  Inside the chain the producing GEMM's epilogue leaves both; at the chain's
-    entry one quantisation pass makes what is missing."""
-    rp = getattr(x, "_wg_row_partials", None)
-    have_rp = rp is not None and rp[2] == x._version
-    if getattr(x, "_wg_mx", None) is None or not have_rp:
-        x._wg_mx = quantize_mx_fp8(x, row_partials=not have_rp)
-    return True
+def mx_rows(x):
+    """bf16 activation rows [.., D] (D % 256 == 0; a tensor or a Rows) -> a Rows with what an MX-chain consumer (linear_mxfp8(ln_eps=...))
+    expects: x, its e4m3 + block-scale form and its rows' partial sums.  Inside the chain the producing GEMM's epilogue leaves both; at
+    the chain's entry one quantisation pass makes what is missing."""
+    r = x if isinstance(x, Rows) else Rows(x)
+    part, mx = r.fresh()
+    if mx is None or part is None:
+        got = quantize_mx_fp8(r.x, row_partials=part is None)
+        r = Rows(r.x, got[2] if part is None else part, got[:2])
+    return r
 
 
 def linear_mxfp8(x, w, bias=None, act=ACT_NONE, residual=None, res_row_mod=0, out=None, ln_eps=None, mx_out=False, bf16_out=True,
                  row_partials=False):
     """act(dequant(x) @ dequant(w).T + bias) (+ residual) on the persistent fp8 GEMM with MX block scales on both operands.
-    x: (xq uint8 [..., K], x_mx) from quantize_mx_fp8 / an earlier call's mx_out -- or, with ln_eps set, the bf16 tensor such a call
-       returned (it carries its fp8 form and its rows' partial sums): LayerNorm(x) is then folded in and w = fold_layernorm_mx(...);
+    x: a Rows whose mx is read (from an earlier call's mx_out, mx_rows or sam_attention); a bare (xq uint8 [..., K], x_mx) pair from
+       quantize_mx_fp8 stands for Rows(mx=pair).  With ln_eps set its partials are read too: LayerNorm(x) is folded in and
+       w = fold_layernorm_mx(...);
     w: mx_weight(...) / fold_layernorm_mx(...).
-    mx_out: the result also leaves as e4m3 + block scales (attached to the returned tensor as ._wg_mx; with bf16_out=False ONLY so, and
-    the pair is what is returned); row_partials: its rows' {sum, sum of squares} partials are attached as ._wg_row_partials (N % 256 == 0)."""
-    ln = None
-    if ln_eps is not None:
-        xt = x
-        rp, xm = getattr(xt, "_wg_row_partials", None), getattr(xt, "_wg_mx", None)
-        assert rp is not None and xm is not None and rp[2] == xt._version, "linear_mxfp8(ln_eps=...): x must come from a call with mx_out and row_partials"
-        x = xm
-        ln = (rp[0], rp[1])
-    xq, x_mx = x
+    mx_out: the result also leaves as e4m3 + block scales (with bf16_out=False ONLY so); row_partials: with its rows' {sum, sum of
+    squares} partials (N % 256 == 0).  With either the result is a Rows (x None with bf16_out=False), else the bf16 tensor."""
+    ln, xmx = (x if isinstance(x, Rows) else Rows(mx=x)).fresh()
+    if ln_eps is None:
+        ln = None
+    elif ln is None:
+        raise ValueError("linear_mxfp8(ln_eps=...): x has no fresh partials (ops.mx_rows makes them)")
+    if xmx is None:
+        raise ValueError("linear_mxfp8: x has no fresh mx (ops.mx_rows / ops.quantize_mx_fp8 make one)")
+    xq, x_mx = xmx
     wq, w_mx = w["q"], w["mx"]
     _need_gpu(xq, x_mx, wq, w_mx, bias, residual, out)
     assert xq.dtype == torch.uint8 and wq.dtype == torch.uint8 and xq.is_contiguous() and wq.is_contiguous()
@@ -622,7 +628,7 @@ def linear_mxfp8(x, w, bias=None, act=ACT_NONE, residual=None, res_row_mod=0, ou
     assert wq.shape[1] == K and x_mx.shape[0] == K // 32 and w_mx.shape[0] == K // 32
     dev = xq.device
     assert bf16_out or mx_out
-    _forget_sidecars(out)
+    assert ln is None or (ln.shape[0] * 256 == K and ln.shape[1] >= M)
     if out is None and bf16_out:
         out = torch.empty(xq.shape[:-1] + (N,), device=dev, dtype=_BF16)
     ldc = _rows(out)[2] if out is not None else 0
@@ -638,17 +644,13 @@ def linear_mxfp8(x, w, bias=None, act=ACT_NONE, residual=None, res_row_mod=0, ou
     rc = _lib.lib().wg_gemm_mxfp8(xq.data_ptr(), K, x_mx.data_ptr(), x_mx.shape[1], wq.data_ptr(), K, w_mx.data_ptr(), w_mx.shape[1],
                                   None if ln is not None else _ptr(bias),
                                   w["colsum"].data_ptr() if ln is not None else None, w["bias_f32"].data_ptr() if ln is not None else None,
-                                  ln[0].data_ptr() if ln is not None else None, ln[0].shape[0] if ln is not None else 0,
-                                  ln[1] if ln is not None else 0, float(ln_eps) if ln is not None else 0.0,
+                                  ln.data_ptr() if ln is not None else None, ln.shape[0] if ln is not None else 0,
+                                  ln.shape[1] if ln is not None else 0, float(ln_eps) if ln is not None else 0.0,
                                   _ptr(residual), ldr, res_row_mod, _ptr(out), ldc, _ptr(cq), N, _ptr(cmx), cmx.shape[1] if mx_out else 0,
                                   _ptr(part), part.shape[1] if row_partials else 0, M, N, K, act, _stream())
     _checked(ev, rc, "wg_gemm_mxfp8")
-    if not bf16_out:
-        return cq, cmx
-    if mx_out:
-        out._wg_mx = (cq, cmx)
-    if row_partials:
-        out._wg_row_partials = (part, part.shape[1], out._version, M, N)
+    if mx_out or row_partials:
+        return Rows(out, part, (cq, cmx) if mx_out else None)
     return out
 
 

@@ -147,7 +147,7 @@ class Block(nn.Module, _Prepared):
         m = self.mlp
         return self._prep_mx() if ops.mx_chain_ok(self.norm1.weight.shape[0], m.lin1.weight.shape[0]) else self._prep_fp8()
 
-    def rows_mx(self, x, B, grid):
+    def rows_mx(self, r, B, grid):
         """The block as one MX chain on the persistent fp8 GEMM (ops.linear_mxfp8): e4m3 operands with a power-of-two scale per 32
         values on both sides; both LayerNorms folded into the GEMM behind them from the partial sums the GEMM in front left; the
         residual GEMMs (proj, lin2) leave the stream as bf16 AND as the next GEMM's e4m3 operand; the MLP's hidden layer only ever
@@ -156,21 +156,22 @@ class Block(nn.Module, _Prepared):
         statistic stay bf16 / fp32."""
         a, m = self.attn, self.mlp
         w = self._prep_mx()
-        qkv = ops.linear_mxfp8(x, w["qkv"], ln_eps=self.norm1.eps)
+        qkv = ops.linear_mxfp8(r, w["qkv"], ln_eps=self.norm1.eps)
         window = self.window_size if self.window_size > 0 else grid
         o = ops.sam_attention(qkv, a.qkv.bias, a.rel_pos_h, a.rel_pos_w, B, grid, window, a.num_heads, mx_out=True)
-        if not isinstance(o, tuple):       # (head_dim 80, other windows: the attention kernel writes bf16 and the quantisation is a pass of its own)
-            o = ops.quantize_mx_fp8(o)
-        x = ops.linear_mxfp8(o, w["proj"], bias=a.proj.bias, residual=x, mx_out=True, row_partials=True)
-        h = ops.linear_mxfp8(x, w["lin1"], act=m._act_code, ln_eps=self.norm2.eps, mx_out=True, bf16_out=False)
-        return ops.linear_mxfp8(h, w["lin2"], bias=m.lin2.bias, residual=x, mx_out=True, row_partials=True)
+        if o.mx is None:                   # (head_dim 80, other windows: the attention kernel writes bf16 and the quantisation is a pass of its own)
+            o = ops.quantize_mx_fp8(o.x)
+        r = ops.linear_mxfp8(o, w["proj"], bias=a.proj.bias, residual=r.x, mx_out=True, row_partials=True)
+        h = ops.linear_mxfp8(r, w["lin1"], act=m._act_code, ln_eps=self.norm2.eps, mx_out=True, bf16_out=False)
+        return ops.linear_mxfp8(h, w["lin2"], bias=m.lin2.bias, residual=r.x, mx_out=True, row_partials=True)
 
-    def rows_fp8(self, x, B, grid):
+    def rows_fp8(self, r, B, grid):
         """The block on the fp8 GEMM path.  Widths the persistent MX kernel takes run as rows_mx; the rest
         with per-row activation scales: both LayerNorms fused with the per-row quantisation of their output."""
         a, m = self.attn, self.mlp
-        if ops.mx_chain_ok(x.shape[-1], m.lin1.weight.shape[0]) and ops.mx_prepare_rows(x):
-            return self.rows_mx(x, B, grid)
+        x = r.x
+        if ops.mx_chain_ok(x.shape[-1], m.lin1.weight.shape[0]):
+            return self.rows_mx(ops.mx_rows(r), B, grid)
         w = self._prep_fp8()
         q, s = ops.quantize_rows_fp8(x, ln=(self.norm1.weight, self.norm1.bias), eps=self.norm1.eps)
         qkv = ops.linear_fp8(q, s, *w["qkv"], bias=a.qkv.bias)
@@ -180,24 +181,24 @@ class Block(nn.Module, _Prepared):
         x = ops.linear_fp8(q, s, *w["proj"], bias=a.proj.bias, residual=x)
         q, s = ops.quantize_rows_fp8(x, ln=(self.norm2.weight, self.norm2.bias), eps=self.norm2.eps)
         q, s = ops.quantize_rows_fp8(ops.linear_fp8(q, s, *w["lin1"], bias=m.lin1.bias, act=m._act_code))
-        return ops.linear_fp8(q, s, *w["lin2"], bias=m.lin2.bias, residual=x)
+        return ops.Rows(ops.linear_fp8(q, s, *w["lin2"], bias=m.lin2.bias, residual=x))
 
-    def rows(self, x, B, grid):
-        """x [B*grid*grid, D] -> same.  window partition / unpartition live inside the attention kernel."""
+    def rows(self, r, B, grid):
+        """r: ops.Rows of x [B*grid*grid, D] -> the same of the block's output.  window partition / unpartition live inside the attention kernel."""
         a = self.attn
         if not a.use_rel_pos or a.qkv.bias is None:
             raise NotImplementedError("the HIP SAM attention is built for use_rel_pos=True, qkv_bias=True (build_sam.py:56-108)")
         if self.gemm_dtype == "fp8":
-            return self.rows_fp8(x, B, grid)
+            return self.rows_fp8(r, B, grid)
         p = self._prep_bf16()
-        qkv = ops.ln_linear(x, p["qkv"], self.norm1.eps)
+        qkv = ops.ln_linear(r, p["qkv"], self.norm1.eps)
         window = self.window_size if self.window_size > 0 else grid
         o = ops.sam_attention(qkv, a.qkv.bias, a.rel_pos_h, a.rel_pos_w, B, grid, window, a.num_heads)
         # proj and lin2 write the residual stream that norm2 / the next block's norm1 read: they leave the rows' partial sums next
-        # to them and ln_linear picks those up (no statistics pass in between)
-        x = ops.linear(o, a.proj.weight, a.proj.bias, residual=x, row_partials=True)
-        h = ops.ln_linear(x, p["lin1"], self.norm2.eps, act=self.mlp._act_code)
-        return ops.linear(h, p["lin2_w"], self.mlp.lin2.bias, residual=x, row_partials=True)
+        # to them (ops.Rows) and ln_linear picks those up (no statistics pass in between)
+        r = ops.linear(o, a.proj.weight, a.proj.bias, residual=r.x, row_partials=True)
+        h = ops.ln_linear(r, p["lin1"], self.norm2.eps, act=self.mlp._act_code)
+        return ops.linear(h, p["lin2_w"], self.mlp.lin2.bias, residual=r.x, row_partials=True)
 
     def _build(self):
         a, m = self.attn, self.mlp
@@ -275,7 +276,7 @@ class ImageEncoderViT(nn.Module, _Prepared):
                        row_partials=True)      # block 0's norm1 reads these rows: the GEMM leaves their statistics with them
         for blk in self.blocks:
             t = blk.rows(t, B, g)
-        t = ops.linear(t, p["neck0_w"])
+        t = ops.linear(t.x, p["neck0_w"])
         t = ops.layernorm(t, self.neck[1].weight, self.neck[1].bias, self.neck[1].eps)
         t = ops.linear(ops.im2row3x3(t, B, g, g), p["neck2_w"])
         return ops.layernorm(t, self.neck[3].weight, self.neck[3].bias, self.neck[3].eps, out=out)
