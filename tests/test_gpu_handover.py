@@ -1,6 +1,7 @@
 """The hand-over of a GEMM's by-products (ops.Rows: row partial sums, the e4m3 copy) through a whole encoder, bf16 and fp8: which GEMM
 kernels are launched, in which order, and how many statistics / quantisation passes run beside them.  The golden encoders are too narrow
-or have too few rows for the persistent kernel; these two are the smallest that reach it (D = 256: 64 tiles of 256 x 256 at M = 16384)."""
+or have too few rows for the persistent kernel; the two D = 256 encoders are the smallest that reach it (64 tiles of 256 x 256 at
+M = 16384).  The two D = 128 encoders are too narrow for the MX chain and take the per-row fp8 chain (ops.linear_fp8)."""
 from functools import partial
 from types import SimpleNamespace
 
@@ -25,9 +26,10 @@ def _assert_chain_shapes_take_the_persistent_kernel(M, producers_k):
         assert L.wg_gemm_ln_supported(M, N, D, D, D, N) == 1, (M, N, D)
 
 
-def _run_counted(fn):
-    """fn() under time_gemms with ops.row_stats / ops.quantize_mx_fp8 counted -> (kernel ids, row_stats calls, quantize_mx_fp8 kwargs)."""
-    counts = {"row_stats": [], "quantize_mx_fp8": []}
+def _run_counted(fn, rows_fp8=None):
+    """fn() under time_gemms with ops.row_stats / ops.quantize_mx_fp8 counted -> (kernel ids, row_stats calls, quantize_mx_fp8 kwargs).
+    rows_fp8: a list that receives the kwargs of every ops.quantize_rows_fp8 call of the same run."""
+    counts = {"row_stats": [], "quantize_mx_fp8": [], "quantize_rows_fp8": [] if rows_fp8 is None else rows_fp8}
     originals = {k: getattr(ops, k) for k in counts}
 
     def counting(name):
@@ -95,7 +97,46 @@ def test_clip_encoder_hands_by_products_from_gemm_to_gemm(dev, clip_transformer,
     _assert_chain_shapes_take_the_persistent_kernel(B * tokens, (D, HIDDEN))                # out_proj, fc2
     for layer in clip_transformer.encoder.layers:
         layer.gemm_dtype = gemm_dtype
-        layer._prep_get(layer._build) if gemm_dtype == "bf16" else layer._prep_get(layer._build_mx, slot="_mx")
+        layer.prepare()
     x = torch.randn(B, 3, 448, 448, device=dev, generator=torch.Generator(dev).manual_seed(22)).to(torch.bfloat16)
     got = _run_counted(lambda: list(clip_transformer.hidden_states(x, None, [0, 1, 2]).values()))
     assert got == (ids, row_stats, quantize)
+
+
+def _narrow_sam(dev):
+    """The "tiny" golden geometry cut to two blocks (one windowed, one global): M = 1 * 32 * 32 = 1024 rows."""
+    torch.manual_seed(13)
+    enc = ImageEncoderViT(img_size=512, patch_size=16, embed_dim=128, depth=2, num_heads=2, mlp_ratio=4, norm_layer=partial(torch.nn.LayerNorm, eps=1e-6),
+                          qkv_bias=True, use_rel_pos=True, global_attn_indexes=(1,), window_size=14, out_chans=256).to(dev).bfloat16().eval()
+    x = torch.randn(1, 3, 512, 512, device=dev, generator=torch.Generator(dev).manual_seed(14)).to(torch.bfloat16)
+    return enc.blocks, enc.prepare, lambda: [enc.forward_tokens(x)]
+
+
+def _narrow_clip(dev):
+    """M = 2 * (64 + 1) = 130 rows."""
+    torch.manual_seed(23)
+    cfg = SimpleNamespace(hidden_size=128, intermediate_size=512, num_hidden_layers=2, num_attention_heads=2, image_size=112, patch_size=14,
+                          layer_norm_eps=1e-5)
+    tower = _CLIPVisionTransformer(cfg).to(dev).bfloat16().eval()
+    x = torch.randn(2, 3, 112, 112, device=dev, generator=torch.Generator(dev).manual_seed(24)).to(torch.bfloat16)
+    layers = tower.encoder.layers
+    return layers, lambda: [layer.prepare() for layer in layers], lambda: list(tower.hidden_states(x, None, [0, 1, 2]).values())
+
+
+# Widths the MX chain does not take (D = 128): the per-row fp8 chain.  Per block four linear_fp8 GEMMs (kernel id 20) in a row, no statistics
+# pass, no MX quantisation, four per-row quantisations of which the first and third are fused with a LayerNorm.  The ids around the chain
+# (patch embedding, neck) are what the tile selector picks at these shapes: recorded from the commit before both encoders shared one block.
+@pytest.mark.parametrize("make,ids", [
+    (_narrow_sam, [11] + [20] * 8 + [11, 11]),
+    (_narrow_clip, [5, 5] + [20] * 8),                      # one patch-embedding GEMM per image
+], ids=["sam", "clip"])
+def test_narrow_encoder_takes_the_per_row_fp8_chain(dev, make, ids):
+    assert not ops.mx_chain_ok(128, 512)
+    blocks, prepare, forward = make(dev)
+    for blk in blocks:
+        blk.gemm_dtype = "fp8"
+    prepare()                                               # the quantised weights first: the counts are the forward's own
+    rows_fp8 = []
+    got = _run_counted(forward, rows_fp8)
+    assert got == (ids, 0, [])
+    assert [sorted(kw) for kw in rows_fp8] == [["eps", "ln"], [], ["eps", "ln"], []] * len(blocks)

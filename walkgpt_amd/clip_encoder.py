@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .segment_anything.modeling import _check_bf16_gpu, _Prepared
+from .encoder_block import PreLNBlock, _check_bf16_gpu, _Prepared
 
 BF16 = torch.bfloat16
 
@@ -59,7 +59,9 @@ class _Mlp(nn.Module):
         self.fc1, self.fc2 = nn.Linear(D, inner), nn.Linear(inner, D)
 
 
-class _EncoderLayer(nn.Module, _Prepared):
+class _EncoderLayer(nn.Module, PreLNBlock):
+    """HF CLIPEncoderLayer as a PreLNBlock: pre-LN attention + pre-LN quick-GELU MLP, both residual."""
+
     def __init__(self, cfg):
         super().__init__()
         D = cfg.hidden_size
@@ -68,74 +70,21 @@ class _EncoderLayer(nn.Module, _Prepared):
         self.mlp = _Mlp(D, cfg.intermediate_size)
         self.layer_norm2 = nn.LayerNorm(D, eps=cfg.layer_norm_eps)
 
-    def _build(self):
-        a, n1, n2, m = self.self_attn, self.layer_norm1, self.layer_norm2, self.mlp
-        w = torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0).contiguous()
-        b = torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias], 0).contiguous()
-        return {"qkv": ops.fold_layernorm(n1.weight, n1.bias, w, b),
-                "fc1": ops.fold_layernorm(n2.weight, n2.bias, m.fc1.weight, m.fc1.bias)}
-
-    gemm_dtype = "bf16"   # "fp8": q|k|v / out_proj / fc1 / fc2 on e4m3 operands (BASELINE config C5); set through WalkGPTGrounding.set_gemm_dtype
-
-    def _build_fp8(self):
+    def _parts(self):
         a, m = self.self_attn, self.mlp
-        wqkv = torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0).contiguous()
-        return {"qkv": ops.quantize_weight_fp8(wqkv), "bqkv": torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias], 0).contiguous(),
-                "out": ops.quantize_weight_fp8(a.out_proj.weight), "fc1": ops.quantize_weight_fp8(m.fc1.weight),
-                "fc2": ops.quantize_weight_fp8(m.fc2.weight)}
+        return (self.layer_norm1, self.layer_norm2, (a.q_proj.weight, a.k_proj.weight, a.v_proj.weight), (a.q_proj.bias, a.k_proj.bias, a.v_proj.bias),
+                a.out_proj, m.fc1, m.fc2, ops.ACT_QUICK_GELU)
 
-    def _build_mx(self):
-        a, n1, n2, m = self.self_attn, self.layer_norm1, self.layer_norm2, self.mlp
-        w = torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0).contiguous()
-        b = torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias], 0).contiguous()
-        return {"qkv": ops.fold_layernorm_mx(n1.weight, n1.bias, w, b), "out": ops.mx_weight(a.out_proj.weight),
-                "fc1": ops.fold_layernorm_mx(n2.weight, n2.bias, m.fc1.weight, m.fc1.bias), "fc2": ops.mx_weight(m.fc2.weight)}
-
-    def run_mx(self, r, key_bias):
-        """The layer as one MX chain on the persistent fp8 GEMM (as Block.rows_mx of the SAM encoder)."""
-        a, m = self.self_attn, self.mlp
-        w = self._prep_get(self._build_mx, slot="_mx")
-        D = r.x.shape[-1]
-        qkv = ops.linear_mxfp8(r, w["qkv"], ln_eps=self.layer_norm1.eps)
-        o = ops.mha(qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:], a.num_heads, a.scale, key_bias, small=False)
-        r = ops.linear_mxfp8(ops.quantize_mx_fp8(o), w["out"], bias=a.out_proj.bias, residual=r.x, mx_out=True, row_partials=True)
-        h = ops.linear_mxfp8(r, w["fc1"], act=ops.ACT_QUICK_GELU, ln_eps=self.layer_norm2.eps, mx_out=True, bf16_out=False)
-        return ops.linear_mxfp8(h, w["fc2"], bias=m.fc2.bias, residual=r.x, mx_out=True, row_partials=True)
-
-    def run_fp8(self, r, key_bias):
-        """The layer on the fp8 GEMM path (as Block.rows_fp8 of the SAM encoder): the MX chain where the widths allow it, otherwise per-row
-        activation scales with both LayerNorms fused into the quantisation of their output.  Attention, the residual stream and every
-        statistic stay bf16 / fp32."""
-        a, m = self.self_attn, self.mlp
-        x = r.x
-        if ops.mx_chain_ok(x.shape[-1], m.fc1.weight.shape[0]):
-            return self.run_mx(ops.mx_rows(r), key_bias)
-        w = self._prep_get(self._build_fp8, (a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, a.out_proj.weight, m.fc1.weight, m.fc2.weight,
-                                             a.q_proj.bias, a.k_proj.bias, a.v_proj.bias), slot="_fp8")
-        D = x.shape[-1]
-        q, s = ops.quantize_rows_fp8(x, ln=(self.layer_norm1.weight, self.layer_norm1.bias), eps=self.layer_norm1.eps)
-        qkv = ops.linear_fp8(q, s, *w["qkv"], bias=w["bqkv"])
-        o = ops.mha(qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:], a.num_heads, a.scale, key_bias, small=False)
-        q, s = ops.quantize_rows_fp8(o)
-        x = ops.linear_fp8(q, s, *w["out"], bias=a.out_proj.bias, residual=x)
-        q, s = ops.quantize_rows_fp8(x, ln=(self.layer_norm2.weight, self.layer_norm2.bias), eps=self.layer_norm2.eps)
-        q, s = ops.quantize_rows_fp8(ops.linear_fp8(q, s, *w["fc1"], bias=m.fc1.bias, act=ops.ACT_QUICK_GELU))
-        return ops.Rows(ops.linear_fp8(q, s, *w["fc2"], bias=m.fc2.bias, residual=x))
+    def _attend(self, qkv, key_bias, mx_out):
+        """Flash attention with the additive key-padding mask on three column slices of the packed rows; its output is bf16 in every chain."""
+        a = self.self_attn
+        D = qkv.shape[-1] // 3
+        return ops.mha(qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:], a.num_heads, a.scale, key_bias, small=False)
 
     def run(self, r, key_bias, tail_tiles=False):
-        """HF CLIPEncoderLayer: pre-LN attention + pre-LN quick-GELU MLP, both residual.  r: ops.Rows of x [B, L, D] -> the same of the output.
-        Both LayerNorms are folded into the GEMM behind them (ops.ln_linear).  tail_tiles: let the M = B*1025 GEMMs use the
+        """r: ops.Rows of x [B, L, D] -> the same of the layer's output.  tail_tiles: let the M = B*1025 GEMMs of the bf16 chain use the
         tail-absorbing tiles (faster when nothing else shares the GPU, slower under stream overlap)."""
-        if self.gemm_dtype == "fp8":
-            return self.run_fp8(r, key_bias)
-        a = self.self_attn
-        p = self._prep_get(self._build)
-        D = r.x.shape[-1]
-        qkv = ops.ln_linear(r, p["qkv"], self.layer_norm1.eps, tail_tiles=tail_tiles)
-        o = ops.mha(qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:], a.num_heads, a.scale, key_bias, small=False)
-        r = ops.linear(o, a.out_proj.weight, a.out_proj.bias, residual=r.x, tail_tiles=tail_tiles, row_partials=True)
-        h = ops.ln_linear(r, p["fc1"], self.layer_norm2.eps, act=ops.ACT_QUICK_GELU, tail_tiles=tail_tiles)
-        return ops.linear(h, self.mlp.fc2.weight, self.mlp.fc2.bias, residual=r.x, tail_tiles=tail_tiles, row_partials=True)
+        return self._block(r, key_bias, tail_tiles)
 
 
 class _Encoder(nn.Module):

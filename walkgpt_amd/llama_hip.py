@@ -270,12 +270,11 @@ class LlamaHipRunner:
     def _weight_key(self):
         """What a captured decode step has baked in: data_ptr, _version and dtype of every weight, and per adapted projection the adapter's
         name, the same of its A and B, and its scaling.  A merged or disabled adapter is absent from it, so switching one changes the key."""
-        ident = lambda t: (t.data_ptr(), t._version, t.dtype)
-        key = [ident(t) for t in (self.llm.model.norm.weight, self._head(), self.llm.get_input_embeddings().weight)]
+        key = [tensor_key(t) for t in (self.llm.model.norm.weight, self._head(), self.llm.get_input_embeddings().weight)]
         for lw in self._layers():
-            key += [ident(t) for t in lw[:9]]
+            key += [tensor_key(t) for t in lw[:9]]
             if lw[9] is not None:
-                key.append(tuple(None if ad is None else (ad[0], ident(ad[1]), ident(ad[2]), ad[3]) for ad in lw[9]))
+                key.append(tuple(None if ad is None else (ad[0], tensor_key(ad[1]), tensor_key(ad[2]), ad[3]) for ad in lw[9]))
         return tuple(key)
 
     # -- the e4m3 store ----------------------------------------------------------------------------------------------------------------------

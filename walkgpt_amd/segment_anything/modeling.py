@@ -18,30 +18,9 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..encoder_block import PreLNBlock, _check_bf16_gpu, _Prepared, _tiled  # noqa: F401  (callers and tests import the last three from here)
 
 BF16 = torch.bfloat16
-
-
-class _Prepared:
-    """Derived (re-laid / concatenated / bf16) kernel operands, rebuilt after any parameter change."""
-
-    def _prep_get(self, build, deps=None, slot=""):
-        """deps: the tensors `build` reads (default: every parameter below this module -- pass them explicitly where the module
-        tree is large, the key is recomputed on every forward).  slot: a second, independently keyed set on the same module."""
-        if deps is None:
-            deps = self.parameters(recurse=True)
-        key = tuple((p.data_ptr(), p._version, p.dtype, p.device) for p in deps if p is not None)
-        if getattr(self, "_prep_key" + slot, None) != key:
-            object.__setattr__(self, "_prep_val" + slot, build())
-            object.__setattr__(self, "_prep_key" + slot, key)
-        return getattr(self, "_prep_val" + slot)
-
-
-def _check_bf16_gpu(t, what):
-    if not t.is_cuda or t.dtype != BF16:
-        raise RuntimeError("%s must be a bf16 GPU tensor for the walkgpt_amd HIP path (got %s on %s); "
-                           "cast the model and inputs with .bfloat16().cuda() -- there is no CPU fallback"
-                           % (what, t.dtype, t.device))
 
 
 class LayerNorm2d(nn.Module):
@@ -98,8 +77,8 @@ class Attention(nn.Module):
             self.rel_pos_w = nn.Parameter(torch.zeros(2 * input_size[1] - 1, head_dim))
 
 
-class Block(nn.Module, _Prepared):
-    """image_encoder.py:130-193.  norm1 / norm2 are folded into the qkv / lin1 GEMMs behind them (ops.ln_linear)."""
+class Block(nn.Module, PreLNBlock):
+    """image_encoder.py:130-193 as a PreLNBlock: norm1 / norm2 are folded into the qkv / lin1 GEMMs behind them."""
 
     def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=True, norm_layer=nn.LayerNorm, act_layer=nn.GELU,
                  use_rel_pos=False, rel_pos_zero_init=True, window_size=0, input_size=None):
@@ -112,105 +91,24 @@ class Block(nn.Module, _Prepared):
         self.mlp = MLPBlock(embedding_dim=dim, mlp_dim=int(dim * mlp_ratio), act=act_layer)
         self.window_size = window_size
 
-    gemm_dtype = "bf16"   # "fp8": qkv / proj / lin1 / lin2 on e4m3 operands (BASELINE config C5); set through WalkGPTGrounding.set_gemm_dtype
-
-    def _build_fp8(self):
+    def _parts(self):
         a, m = self.attn, self.mlp
-        return {k: ops.quantize_weight_fp8(w) for k, w in (("qkv", a.qkv.weight), ("proj", a.proj.weight), ("lin1", m.lin1.weight),
-                                                           ("lin2", m.lin2.weight))}
+        return self.norm1, self.norm2, (a.qkv.weight,), (a.qkv.bias,), a.proj, m.lin1, m.lin2, m._act_code
 
-    def _build_mx(self):
-        a, m = self.attn, self.mlp
-        return {"qkv": ops.fold_layernorm_mx(self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias), "proj": ops.mx_weight(a.proj.weight),
-                "lin1": ops.fold_layernorm_mx(self.norm2.weight, self.norm2.bias, m.lin1.weight, m.lin1.bias), "lin2": ops.mx_weight(m.lin2.weight)}
-
-    # the derived operands of the three GEMM paths, each keyed on the parameters it reads
-    def _prep_bf16(self):
-        a, m = self.attn, self.mlp
-        return self._prep_get(self._build, (self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias, self.norm2.weight, self.norm2.bias,
-                                            m.lin1.weight, m.lin1.bias, m.lin2.weight))
-
-    def _prep_mx(self):
-        a, m = self.attn, self.mlp
-        return self._prep_get(self._build_mx, (self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias, a.proj.weight, self.norm2.weight,
-                                               self.norm2.bias, m.lin1.weight, m.lin1.bias, m.lin2.weight), slot="_mx")
-
-    def _prep_fp8(self):
-        a, m = self.attn, self.mlp
-        return self._prep_get(self._build_fp8, (a.qkv.weight, a.proj.weight, m.lin1.weight, m.lin2.weight), slot="_fp8")
-
-    def prepare(self):
-        """Build (or refresh) the derived operands rows() will read, on the CURRENT stream: a caller that runs slices of a batch on side streams
-        calls this before it forks, so that no slice builds them lazily on one stream while another reads them unordered."""
-        if self.gemm_dtype != "fp8":
-            return self._prep_bf16()
-        m = self.mlp
-        return self._prep_mx() if ops.mx_chain_ok(self.norm1.weight.shape[0], m.lin1.weight.shape[0]) else self._prep_fp8()
-
-    def rows_mx(self, r, B, grid):
-        """The block as one MX chain on the persistent fp8 GEMM (ops.linear_mxfp8): e4m3 operands with a power-of-two scale per 32
-        values on both sides; both LayerNorms folded into the GEMM behind them from the partial sums the GEMM in front left; the
-        residual GEMMs (proj, lin2) leave the stream as bf16 AND as the next GEMM's e4m3 operand; the MLP's hidden layer only ever
-        exists as e4m3.  At head_dim 64 the attention kernels write their output as the proj GEMM's MX operand themselves (round 4); at ViT-H's 80 a
-        32-column block would straddle two heads and the attention output keeps one quantisation pass per block.  Attention, the residual stream and every
-        statistic stay bf16 / fp32."""
-        a, m = self.attn, self.mlp
-        w = self._prep_mx()
-        qkv = ops.linear_mxfp8(r, w["qkv"], ln_eps=self.norm1.eps)
+    def _attend(self, qkv, ctx, mx_out):
+        """window partition / unpartition live inside the attention kernel; with mx_out it writes the proj GEMM's MX operand itself where it can
+        (head_dim 64; window 14 or the 64 x 64 global grid)."""
+        a = self.attn
+        B, grid = ctx
         window = self.window_size if self.window_size > 0 else grid
-        o = ops.sam_attention(qkv, a.qkv.bias, a.rel_pos_h, a.rel_pos_w, B, grid, window, a.num_heads, mx_out=True)
-        if o.mx is None:                   # (head_dim 80, other windows: the attention kernel writes bf16 and the quantisation is a pass of its own)
-            o = ops.quantize_mx_fp8(o.x)
-        r = ops.linear_mxfp8(o, w["proj"], bias=a.proj.bias, residual=r.x, mx_out=True, row_partials=True)
-        h = ops.linear_mxfp8(r, w["lin1"], act=m._act_code, ln_eps=self.norm2.eps, mx_out=True, bf16_out=False)
-        return ops.linear_mxfp8(h, w["lin2"], bias=m.lin2.bias, residual=r.x, mx_out=True, row_partials=True)
-
-    def rows_fp8(self, r, B, grid):
-        """The block on the fp8 GEMM path.  Widths the persistent MX kernel takes run as rows_mx; the rest
-        with per-row activation scales: both LayerNorms fused with the per-row quantisation of their output."""
-        a, m = self.attn, self.mlp
-        x = r.x
-        if ops.mx_chain_ok(x.shape[-1], m.lin1.weight.shape[0]):
-            return self.rows_mx(ops.mx_rows(r), B, grid)
-        w = self._prep_fp8()
-        q, s = ops.quantize_rows_fp8(x, ln=(self.norm1.weight, self.norm1.bias), eps=self.norm1.eps)
-        qkv = ops.linear_fp8(q, s, *w["qkv"], bias=a.qkv.bias)
-        window = self.window_size if self.window_size > 0 else grid
-        o = ops.sam_attention(qkv, a.qkv.bias, a.rel_pos_h, a.rel_pos_w, B, grid, window, a.num_heads)
-        q, s = ops.quantize_rows_fp8(o)
-        x = ops.linear_fp8(q, s, *w["proj"], bias=a.proj.bias, residual=x)
-        q, s = ops.quantize_rows_fp8(x, ln=(self.norm2.weight, self.norm2.bias), eps=self.norm2.eps)
-        q, s = ops.quantize_rows_fp8(ops.linear_fp8(q, s, *w["lin1"], bias=m.lin1.bias, act=m._act_code))
-        return ops.Rows(ops.linear_fp8(q, s, *w["lin2"], bias=m.lin2.bias, residual=x))
+        return ops.sam_attention(qkv, a.qkv.bias, a.rel_pos_h, a.rel_pos_w, B, grid, window, a.num_heads, mx_out=mx_out)
 
     def rows(self, r, B, grid):
-        """r: ops.Rows of x [B*grid*grid, D] -> the same of the block's output.  window partition / unpartition live inside the attention kernel."""
+        """r: ops.Rows of x [B*grid*grid, D] -> the same of the block's output."""
         a = self.attn
         if not a.use_rel_pos or a.qkv.bias is None:
             raise NotImplementedError("the HIP SAM attention is built for use_rel_pos=True, qkv_bias=True (build_sam.py:56-108)")
-        if self.gemm_dtype == "fp8":
-            return self.rows_fp8(r, B, grid)
-        p = self._prep_bf16()
-        qkv = ops.ln_linear(r, p["qkv"], self.norm1.eps)
-        window = self.window_size if self.window_size > 0 else grid
-        o = ops.sam_attention(qkv, a.qkv.bias, a.rel_pos_h, a.rel_pos_w, B, grid, window, a.num_heads)
-        # proj and lin2 write the residual stream that norm2 / the next block's norm1 read: they leave the rows' partial sums next
-        # to them (ops.Rows) and ln_linear picks those up (no statistics pass in between)
-        r = ops.linear(o, a.proj.weight, a.proj.bias, residual=r.x, row_partials=True)
-        h = ops.ln_linear(r, p["lin1"], self.norm2.eps, act=self.mlp._act_code)
-        return ops.linear(h, p["lin2_w"], self.mlp.lin2.bias, residual=r.x, row_partials=True)
-
-    def _build(self):
-        a, m = self.attn, self.mlp
-        w2 = m.lin2.weight
-        if (w2.shape[1] * 2) % 10240 == 0 and w2.is_cuda:
-            # ViT-H's lin2 (K = 5120): weight rows on a 10 240-byte pitch camp on a few memory channels -- the same rows 128 bytes further apart run the
-            # GEMM 10 % faster (tools/bench_gemm_pitch.py, notes/r06_experiments.md section 7; K = 3072 / 4096 rows measured no difference)
-            buf = torch.empty(w2.shape[0], w2.shape[1] + 64, device=w2.device, dtype=w2.dtype)
-            buf[:, :w2.shape[1]].copy_(w2.detach())
-            w2 = buf[:, :w2.shape[1]]
-        return {"qkv": ops.fold_layernorm(self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias),
-                "lin1": ops.fold_layernorm(self.norm2.weight, self.norm2.bias, m.lin1.weight, m.lin1.bias), "lin2_w": w2}
+        return self._block(r, (B, grid))
 
 
 class ImageEncoderViT(nn.Module, _Prepared):
@@ -331,21 +229,21 @@ class PromptEncoder(nn.Module, _Prepared):
             nn.Conv2d(mask_in_chans, embed_dim, kernel_size=1),
         )
         self.no_mask_embed = nn.Embedding(1, embed_dim)
-        self._pe_cache = None
+
+    def _dense_pe(self):
+        """(fp32, bf16) [h*w, C] rows of the dense positional encoding; input independent, rebuilt when the gaussian matrix moves or is edited."""
+        def build():
+            pe32 = self.pe_layer.tokens(self.image_embedding_size)
+            return pe32, ops.cast_bf16(pe32)
+        return self._prep_get(build, (self.pe_layer.positional_encoding_gaussian_matrix,), slot="_pe")
 
     def dense_pe_tokens(self) -> torch.Tensor:
-        """bf16 [h*w, C] rows of get_dense_pe(); input independent, cached per (device, buffer version)."""
-        G = self.pe_layer.positional_encoding_gaussian_matrix
-        key = (G.data_ptr(), G._version, G.device)
-        if self._pe_cache is None or self._pe_cache[0] != key:
-            pe32 = self.pe_layer.tokens(self.image_embedding_size)
-            self._pe_cache = (key, pe32, ops.cast_bf16(pe32))
-        return self._pe_cache[2]
+        """bf16 [h*w, C] rows of get_dense_pe()."""
+        return self._dense_pe()[1]
 
     def get_dense_pe(self) -> torch.Tensor:
-        self.dense_pe_tokens()
         h, w = self.image_embedding_size
-        return self._pe_cache[1].t().reshape(1, -1, h, w)
+        return self._dense_pe()[0].t().reshape(1, -1, h, w)
 
     def _point_params(self):
         return list(self.point_embeddings.parameters()) + list(self.not_a_point_embed.parameters())
@@ -483,23 +381,11 @@ def _interleave_kv_heads(wcat, rtab, d, heads):
     return wcat[idx].contiguous(), rtab[:, idx].contiguous()
 
 
-import weakref
-
-_TILED = {}   # id(weight Parameter) -> (weak reference, identity key, fragment-order copy); tensors compare element-wise, so no WeakKeyDictionary
-
-
-def _tiled(weight, k_slices=1):
-    """ops.tile_weight(weight), cached until the parameter's storage, version, dtype or device changes (the token-side decoder kernels
-    stream their weight matrices in MFMA fragment order; the copy is made once per checkpoint)."""
-    key = (weight.data_ptr(), weight._version, weight.dtype, str(weight.device), k_slices)
-    wid = id(weight)
-    ent = _TILED.get(wid)
-    if ent is None or ent[0]() is not weight or ent[1] != key:
-        with torch.no_grad():
-            tiled = ops.tile_weight(weight.detach().contiguous(), k_slices)
-        ent = (weakref.ref(weight, lambda _r, wid=wid: _TILED.pop(wid, None)), key, tiled)
-        _TILED[wid] = ent
-    return ent[2]
+def _image_side_table(owner, slot, pe_tokens, parts, d, heads, src_bias=None):
+    """(Wcat, R) of _pe_folded_projection(pe_tokens, parts, src_bias) with its K | V columns interleaved per head (d: their width), cached on
+    `owner` under `slot` per positional-encoding tensor / weights and biases of `parts` / constant row."""
+    return owner._prep_get(lambda: _interleave_kv_heads(*_pe_folded_projection(pe_tokens.reshape(-1, pe_tokens.shape[-1]), parts, src_bias), d, heads),
+                           [pe_tokens] + [lin.weight for lin, _ in parts] + [lin.bias for lin, _ in parts] + [src_bias], slot)
 
 
 def _lin_pair(lin):
@@ -507,7 +393,7 @@ def _lin_pair(lin):
     return [_tiled(lin.weight), lin.bias]
 
 
-class TwoWayAttentionBlock(nn.Module):
+class TwoWayAttentionBlock(nn.Module, _Prepared):
     def __init__(self, embedding_dim, num_heads, mlp_dim=2048, activation=nn.ReLU, attention_downsample_rate=2,
                  skip_first_layer_pe=False):
         super().__init__()
@@ -521,27 +407,13 @@ class TwoWayAttentionBlock(nn.Module):
         self.cross_attn_image_to_token = DecoderAttention(embedding_dim, num_heads, downsample_rate=attention_downsample_rate)
         self.skip_first_layer_pe = skip_first_layer_pe
 
-    def _image_side(self, key_pe, src_bias=None):
-        """[(K_h | V_h of token->image, per head) | Q_i2t] of the image tokens as one GEMM (cached per positional-encoding tensor / weights /
-        constant row)."""
-        t2i, i2t = self.cross_attn_token_to_image, self.cross_attn_image_to_token
-        key = (key_pe.data_ptr(), key_pe._version) + tuple((p.data_ptr(), p._version) for p in
-                                                           (t2i.k_proj.weight, t2i.v_proj.weight, i2t.q_proj.weight,
-                                                            t2i.k_proj.bias, t2i.v_proj.bias, i2t.q_proj.bias))
-        if src_bias is not None:
-            key += (src_bias.data_ptr(), src_bias._version)
-        if getattr(self, "_img_key", None) != key:
-            self._img_val = _interleave_kv_heads(*_pe_folded_projection(key_pe.reshape(-1, key_pe.shape[-1]),
-                                                                        [(t2i.k_proj, True), (t2i.v_proj, False), (i2t.q_proj, True)], src_bias),
-                                                 t2i.internal_dim, t2i.num_heads)
-            self._img_key = key
-        return self._img_val
-
     def image_side(self, keys, key_pe, src_bias=None):
         """[K_t2i | V_t2i | Q_i2t] of this block's image tokens: the three projections that read `keys` (the reference recomputes
         keys + key_pe for two of them) as one fused GEMM with the positional term folded into an additive table.  src_bias [1, C]:
         the block's image tokens are keys + src_bias (mask_decoder.py:136: the dense no-mask embedding), never materialised."""
-        wcat, rtab = self._image_side(key_pe, src_bias)
+        t2i, i2t = self.cross_attn_token_to_image, self.cross_attn_image_to_token
+        wcat, rtab = _image_side_table(self, "_img", key_pe, [(t2i.k_proj, True), (t2i.v_proj, False), (i2t.q_proj, True)], t2i.internal_dim,
+                                       t2i.num_heads, src_bias)
         return ops.linear(keys, wcat, residual=rtab, res_row_mod=keys.shape[1])          # [1|P, hw, 3d]
 
     def fused_i2t_ok(self, keys, n_tokens):
@@ -643,7 +515,7 @@ def token_stage_table(self_blk=None, t2i=None, norm=None, sum_blk=None):
     return w
 
 
-class TwoWayTransformer(nn.Module):
+class TwoWayTransformer(nn.Module, _Prepared):
     """transformer.py:16-106."""
 
     def __init__(self, depth, embedding_dim, num_heads, mlp_dim, activation=nn.ReLU, attention_downsample_rate=2):
@@ -722,13 +594,7 @@ class TwoWayTransformer(nn.Module):
     def final_image_side(self, keys, pe_tokens):
         """[K | V] of the final token->image attention (positional term folded into the additive table)."""
         fa = self.final_attn_token_to_image
-        key = (pe_tokens.data_ptr(), pe_tokens._version) + tuple((p.data_ptr(), p._version) for p in
-                                                                 (fa.k_proj.weight, fa.v_proj.weight, fa.k_proj.bias, fa.v_proj.bias))
-        if getattr(self, "_fin_key", None) != key:
-            self._fin_val = _interleave_kv_heads(*_pe_folded_projection(pe_tokens.reshape(-1, pe_tokens.shape[-1]),
-                                                                        [(fa.k_proj, True), (fa.v_proj, False)]), fa.internal_dim, fa.num_heads)
-            self._fin_key = key
-        wcat, rtab = self._fin_val
+        wcat, rtab = _image_side_table(self, "_fin", pe_tokens, [(fa.k_proj, True), (fa.v_proj, False)], fa.internal_dim, fa.num_heads)
         return ops.linear(keys, wcat, residual=rtab, res_row_mod=keys.shape[1])
 
     def fused_ok(self, n_out_tokens, n_prompt_tokens):

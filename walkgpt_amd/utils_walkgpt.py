@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .segment_anything.modeling import _check_bf16_gpu, _Prepared
+from .encoder_block import _check_bf16_gpu, _Prepared, _tiled
 
 BF16 = torch.bfloat16
 
@@ -152,16 +152,6 @@ class CalibratedTextProjector(nn.Module):
         if self.net[3].bias is not None:
             nn.init.zeros_(self.net[3].bias)
 
-    def _tiled(self, weight):
-        """ops.tile_weight(weight), cached per (storage, version)"""
-        cache = self.__dict__.setdefault("_tiled_cache", {})
-        key = (weight.data_ptr(), weight._version, weight.dtype, str(weight.device))
-        ent = cache.get(id(weight))
-        if ent is None or ent[0] != key:
-            with torch.no_grad():
-                ent = cache[id(weight)] = (key, ops.tile_weight(weight.detach().contiguous()))
-        return ent[1]
-
     def pre_tail(self, x):
         """net[0..3] of :321-323: LayerNorm -> Linear -> GELU -> Linear, [.., in_dim] -> [.., out_dim] (before net[4], text_type, normalise)."""
         _check_bf16_gpu(x, "hidden states")
@@ -170,7 +160,7 @@ class CalibratedTextProjector(nn.Module):
         ln = self.net[0]
         x = x.contiguous()
         few = x.numel() // x.shape[-1] <= 128         # up to 128 [SEG] rows: one-launch skinny GEMMs on weights kept in fragment order
-        t1, t3 = (self._tiled(self.net[1].weight), self._tiled(self.net[3].weight)) if few else (None, None)
+        t1, t3 = (_tiled(self.net[1].weight), _tiled(self.net[3].weight)) if few else (None, None)
         y = ops.layernorm_linear(x, ln.weight, ln.bias, ln.eps, self.net[1].weight, self.net[1].bias, act=ops.ACT_GELU, weight_tiled=t1)
         return ops.layernorm_linear(y, None, None, 0.0, self.net[3].weight, self.net[3].bias, weight_tiled=t3)
 
